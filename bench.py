@@ -9,9 +9,13 @@ A "step" is one pass of the hot path over one batch of FRAMES_PER_STEP independe
 (seeds 1000+k, BASELINE.json configs[4]: 64 frames over 8 GPUs = 8 per GPU).  Frames shard across ranks with
 no data-path collective (weak scaling); RCCL is used only to reduce the timing / keypoint counters.
 
-Output: ONE JSON line on rank 0 (driver contract) with `roofline` (the kernel with the longest average launch among
+Output: ONE JSON line on rank 0 (driver contract).  A plain run sets up, warms up, times the --steps steps and prints the
+headline (`value`, `ms_per_step`, per-rank figures).  With --full the line also carries `sustained`, `roofline` (the kernel
+with the longest average launch among
 fast / harris / nms / bad, against the HBM roofline, timed live with HIP events on the launch stream) and `cpu_baseline` (the oracle timed on the
-host cores, rank 0, N=1 only, one 8K frame).
+host cores, rank 0, N=1 only, one 8K frame), `latency`, `parity_8k_frame0` and `configs`.
+
+--dump-outputs DIR writes what the last timed step returned (rank 0) as .npy files: see dump_outputs().
 """
 import argparse
 import json
@@ -46,6 +50,38 @@ def free_port():
     p = s.getsockname()[1]
     s.close()
     return p
+
+
+DUMP_MAX_FRAMES = 8                # --dump-outputs: the step's first 8 frames ...
+DUMP_DESC_ROWS = 16384             # ... and a fixed, seeded sample of descriptor rows: 7.7 + 33.6 MB at 8K, 40 000 kp
+DUMP_KP_FIELDS = ("x", "y", "response", "angle", "octave", "size")
+
+
+def dump_outputs(out_dir, kps, desc, cnt):
+    """Writes what the caller of the timed path receives for the frames of the last step (frame i: kps[i], desc[i], cnt[i]):
+      counts.npy           float64 [F]              keypoints returned per frame
+      keypoints.npy        float32 [F, 6, NFEATURES] x, y, response, angle, octave, size (the 5-row matrix unpacked,
+                                                     unpack_keypoints); columns at or past a frame's count are set to 0
+      descriptor_rows.npy  float64 [R]              the sampled descriptor rows (seed 0, sorted; the same in every run)
+      descriptors.npy      float32 [F, R, 64]       the BAD512 bytes of those rows; rows at or past a frame's count are -1
+    F = min(frames per step, DUMP_MAX_FRAMES), R = DUMP_DESC_ROWS."""
+    import torch
+    import cef_loader
+    unpack = cef_loader.load().unpack_keypoints
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    nf = min(len(cnt), DUMP_MAX_FRAMES)
+    n = np.array([int(cnt[i].item()) for i in range(nf)])
+    k = np.stack([np.stack([unpack(kps[i].cpu().numpy())[f] for f in DUMP_KP_FIELDS]) for i in range(nf)]).astype(np.float32)
+    k = np.where(np.arange(k.shape[2])[None, None, :] < n[:, None, None], k, np.float32(0))
+    rows = np.sort(np.random.default_rng(0).choice(NFEATURES, DUMP_DESC_ROWS, replace=False))
+    idx = torch.from_numpy(rows).cuda()
+    d = np.stack([desc[i].index_select(0, idx).cpu().numpy() for i in range(nf)]).astype(np.float32)
+    d[rows[None, :] >= n[:, None]] = -1
+    np.save(os.path.join(out_dir, "counts.npy"), n.astype(np.float64))
+    np.save(os.path.join(out_dir, "keypoints.npy"), k)
+    np.save(os.path.join(out_dir, "descriptor_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "descriptors.npy"), d)
 
 
 def launch_ranks(args):
@@ -123,6 +159,11 @@ def main():
     ap.add_argument("--streams", type=int, default=3,
                     help="independent frames in flight per GPU: one context + one HIP stream each (a context is not "
                          "re-entrant, like the reference's EfficientFeaturesImpl; frames are independent)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the live per-kernel HIP-event pairs inside the timed region, `sustained`, "
+                         "`roofline`, `latency`, `cpu_baseline`, `parity_8k_frame0` and `configs` (shaped by --no-cpu-baseline, --no-configs, --config-iters, --sustain-seconds)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/*.npy (rank 0; see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-configs", action="store_true",
                     help="skip the `configs` block (BASELINE.json C2 / C3 / C4 and the README rows, tools/bench_configs.py; N = 1 only)")
@@ -239,8 +280,10 @@ def main():
     # HIP event pairs around the kernels of one frame per step on context 0 (each pair costs a few microseconds of
     # stream idle time, so not on every frame;
     # on the first PROF_STEPS steps only: a long run needs no more samples)
-    PROF_STEPS = min(args.steps, int(os.environ.get("EFX_BENCH_PROF_STEPS", "24")))
-    det.profileEnable(PROF_STEPS * 12 + 12, stride=max(1, F // NS))
+    # (--full only: a plain run times the steps alone)
+    if args.full:
+        PROF_STEPS = min(args.steps, int(os.environ.get("EFX_BENCH_PROF_STEPS", "24")))
+        det.profileEnable(PROF_STEPS * 12 + 12, stride=max(1, F // NS))
     # one event per step and stream (no host wait): per-step spread, reported next to the mean
     marks = [[torch.cuda.Event(enable_timing=True) for _ in range(NS)] for _ in range(args.steps + 1)]
     barrier()
@@ -257,10 +300,13 @@ def main():
     dt = time.perf_counter() - t0
     timed_region_open[0] = False
     assert len(frames) == n_frames_before, "frames were generated inside the timed region"
-    ms, lvl = det.profileRead()
+    if args.full:
+        ms, lvl = det.profileRead()
     # a step is over when its last stream is: time of step k = latest end of step k - latest end of step k-1
     ends = np.array([[marks[0][0].elapsed_time(marks[k][s_]) for s_ in range(NS)] for k in range(args.steps + 1)]).max(axis=1)
     step_ms = np.diff(ends)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, kps, desc, cnt)
 
     nkp = int(sum(int(c.item()) for c in cnt))      # keypoints per step on this rank
     # RCCL over xGMI only for the counters: MAX of the time, SUM of the keypoints
@@ -275,7 +321,7 @@ def main():
 
     # the same steps again for --sustain-seconds when the K timed steps were over sooner (every rank; `value` stays the K steps)
     sustained = None
-    if args.sustain_seconds > 0 and dt < args.sustain_seconds:
+    if args.full and args.sustain_seconds > 0 and dt < args.sustain_seconds:
         for d_ in dets:
             d_.profileEnable(0)
         ks = int(np.ceil(1.15 * args.sustain_seconds / (dt / args.steps)))     # a long run is a little faster per step than a short one
@@ -290,7 +336,32 @@ def main():
                      "ms_per_frame": round(ts_max / ks / F * 1e3, 4),
                      "what": "the timed steps repeated behind the timed region, same barriers, max over ranks"}
 
+    out = None
     if rank == 0:
+        out = {"metric": "Mkeypoints/s detectAndCompute (8K, 40k kp, BAD512)",
+               "value": round(kp_total / t_max / 1e6, 3), "unit": "Mkeypoints/s", "n_gpus": world, "rccl_world": rccl_world, "rccl_exercised": rccl_exercised,
+               "steps": args.steps, "warmup": args.warmup,
+               "ms_per_step": round(t_max / args.steps * 1e3, 4),
+               "ms_per_step_min_median_max": [round(float(step_ms.min()), 4), round(float(np.median(step_ms)), 4), round(float(step_ms.max()), 4)],
+               "ms_per_frame": round(t_max / args.steps / F * 1e3, 4),
+               "higher_is_better": True, "scaling": "weak",
+               "vs_baseline": round(kp_total / t_max / 1e6 / BASELINE_MKPS, 2), "dtype": "u8",
+               "data": "synthetic", "full": args.full,
+               "config": {"workload": "detectAndCompute BAD512 on 8K (7680x4320) synthetic frames, nfeatures=40000, "
+                                      "8 levels, scale 1.2, FAST threshold 20, NMS radius 15 (BASELINE.json configs[4])",
+                          "frames_per_step_per_gpu": F, "frames_per_step": F * world,
+                          "frames_each_once": sorted(sum(all_frames, [])) == list(range(F * world)), "streams_per_gpu": NS,
+                          "frames_per_launch": [len(range(j, F, NS)) for j in range(NS)],
+                          "keypoints_per_frame": round(nkp / F, 1), "parallelism": f"frames sharded over {world} GPU(s)"},
+               "per_rank": {"ms_per_frame": [round(t / args.steps / F * 1e3, 4) for t in per_rank_s],
+                            "value": [round(k * args.steps / t / 1e6, 3) for k, t in zip(per_rank_kp, per_rank_s)],
+                            "slowest_over_fastest": round(max(per_rank_s) / min(per_rank_s), 4),
+                            "setup_seconds": [round(t, 2) for t in per_rank_setup],
+                            "cpus_pinned": [int(n) for n in per_rank_cpus],
+                            "note": "rank r = GPU r; `value` (top level) = all ranks' keypoints / the slowest rank's time; the set-up "
+                                    "(synthetic frames generated and uploaded) lies before the first barrier"}}
+
+    if rank == 0 and args.full:
         px, bytes_frame = detect_algorithmic_bytes(det, ROWS, COLS)
         stats = dets[0].lastLevelStats()
         n_corners = float(sum(s["n_candidates"] for s in stats))      # FAST corners of the last frame of context 0
@@ -467,30 +538,8 @@ def main():
                 roof["lds"] = {"kernel": dom, "lds_array_cycles_per_launch": lc, "cus": 256,
                                "busy_frac": round(lc / 256 / (prof.get("clock_ghz", 2.4) * 1e9) / (iso[dom]["avg_launch_ms"] * 1e-3), 4)}
 
-        out = {"metric": "Mkeypoints/s detectAndCompute (8K, 40k kp, BAD512)",
-               "value": round(kp_total / t_max / 1e6, 3), "unit": "Mkeypoints/s", "n_gpus": world, "rccl_world": rccl_world, "rccl_exercised": rccl_exercised,
-               "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": round(t_max / args.steps * 1e3, 4),
-               "ms_per_step_min_median_max": [round(float(step_ms.min()), 4), round(float(np.median(step_ms)), 4), round(float(step_ms.max()), 4)],
-               "ms_per_frame": round(t_max / args.steps / F * 1e3, 4),
-               "higher_is_better": True, "scaling": "weak",
-               "vs_baseline": round(kp_total / t_max / 1e6 / BASELINE_MKPS, 2), "dtype": "u8",
-               "data": "synthetic",
-               "config": {"workload": "detectAndCompute BAD512 on 8K (7680x4320) synthetic frames, nfeatures=40000, "
-                                      "8 levels, scale 1.2, FAST threshold 20, NMS radius 15 (BASELINE.json configs[4])",
-                          "frames_per_step_per_gpu": F, "frames_per_step": F * world,
-                          "frames_each_once": sorted(sum(all_frames, [])) == list(range(F * world)), "streams_per_gpu": NS,
-                          "frames_per_launch": [len(range(j, F, NS)) for j in range(NS)],
-                          "keypoints_per_frame": round(nkp / F, 1), "parallelism": f"frames sharded over {world} GPU(s)"},
-               "sustained": sustained if sustained else {"note": "the timed region itself lasted %.2f s" % t_max},
-               "per_rank": {"ms_per_frame": [round(t / args.steps / F * 1e3, 4) for t in per_rank_s],
-                            "value": [round(k * args.steps / t / 1e6, 3) for k, t in zip(per_rank_kp, per_rank_s)],
-                            "slowest_over_fastest": round(max(per_rank_s) / min(per_rank_s), 4),
-                            "setup_seconds": [round(t, 2) for t in per_rank_setup],
-                            "cpus_pinned": [int(n) for n in per_rank_cpus],
-                            "note": "rank r = GPU r; `value` (top level) = all ranks' keypoints / the slowest rank's time; the set-up "
-                                    "(synthetic frames generated and uploaded) lies before the first barrier"},
-               "roofline": roof}
+        out["sustained"] = sustained if sustained else {"note": "the timed region itself lasted %.2f s" % t_max}
+        out["roofline"] = roof
         tag = os.path.basename(cfiles[-1])[:3] if cfiles else "rNN"
         roof["profiles"] = {"frac / kernels_isolated (one stream)": "profiles/%s_kernel_stats.csv" % tag,
                             "live (the default command, three frames in flight)": "profiles/%s_kernel_stats_3streams.csv" % tag,
@@ -565,6 +614,7 @@ def main():
             gc.collect()
             from tools import bench_configs
             out["configs"] = bench_configs.measure(cef, iters=args.config_iters, cpu_baseline=not args.no_cpu_baseline)
+    if rank == 0:
         print(json.dumps(out), flush=True)
 
     if dist is not None:

@@ -1,6 +1,7 @@
-"""The driver's contract for bench.py, on the GPU: `python bench.py --gpus 1 --steps K --warmup W` prints ONE JSON line with
+"""The driver's contract for bench.py, on the GPU: `python bench.py --gpus 1 --steps K --warmup W --full` prints ONE JSON line with
 BASELINE.json's metric, the `roofline` and `cpu_baseline` objects and (round 4) the `configs` block, and the product path it
-times equals the oracle on frame 0 (`parity_8k_frame0`).  A short run: the kernels are the same as in the default command."""
+times equals the oracle on frame 0 (`parity_8k_frame0`).  A short run: the kernels are the same as in the default command.
+Without --full the line holds the headline alone; --dump-outputs writes what the last timed step returned."""
 import json
 import os
 import subprocess
@@ -18,7 +19,7 @@ def line():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--config-iters", "3"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--full", "--config-iters", "3"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
@@ -95,3 +96,36 @@ def test_force_dist_runs_rccl_at_world_1():
     j = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")][-1]
     assert j["rccl_exercised"] is True and j["rccl_world"] == 1 and j["n_gpus"] == 1
     assert j["value"] > 20.0 and len(j["per_rank"]["ms_per_frame"]) == 1
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run: the headline fields and nothing of --full; --steps sets the timed steps; --dump-outputs writes the last
+    step's keypoints / descriptor sample / counts as float .npy files (under 64 MB), the same in a second run."""
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    outs = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1",
+                            "--dump-outputs", str(d)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        j = lines[0]
+        assert j["steps"] == 5 and j["warmup"] == 1 and j["full"] is False and j["ms_per_step"] > 0
+        assert j["unit"] == "Mkeypoints/s" and j["higher_is_better"] is True and j["dtype"] == "u8"
+        assert j["value"] == pytest.approx(8 * j["config"]["keypoints_per_frame"] / (j["ms_per_step"] * 1e-3) / 1e6, rel=1e-3)
+        assert not {"sustained", "roofline", "latency", "cpu_baseline", "parity_8k_frame0", "configs"} & set(j)
+        files = {f.name: np.load(f) for f in d.iterdir()}
+        assert set(files) == {"counts.npy", "keypoints.npy", "descriptor_rows.npy", "descriptors.npy"}
+        assert sum(f.stat().st_size for f in d.iterdir()) < 64 * 2 ** 20
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        n = files["counts.npy"]
+        assert n.shape == (8,) and n.sum() == pytest.approx(8 * j["config"]["keypoints_per_frame"], abs=1)
+        assert files["keypoints.npy"].shape == (8, 6, 40000) and files["descriptors.npy"].shape[::2] == (8, 64)
+        outs.append(files)
+    for name in outs[0]:
+        assert np.array_equal(outs[0][name], outs[1][name]), name

@@ -15,5 +15,5 @@ rows=[r for r in csv.reader(open("gpurun_out/sw_kernel_stats.csv")) if r and r[0
 frames=53
 print("   chain us per frame:", round(sum(float(r[2]) for r in rows)/frames,1), " launches per frame:", sum(int(r[1]) for r in rows)/frames)
 PY
-  python bench.py --steps 60 --warmup 3 --no-cpu-baseline --no-configs --sustain-seconds 0 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('   value', d['value'], 'ms/frame', d['ms_per_frame'], 'latency', d['latency']['ms_per_frame'], 'parity-free')"
+  python bench.py --steps 60 --warmup 3 --full --no-cpu-baseline --no-configs --sustain-seconds 0 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('   value', d['value'], 'ms/frame', d['ms_per_frame'], 'latency', d['latency']['ms_per_frame'], 'parity-free')"
 done
