@@ -103,6 +103,15 @@ static BlockCache& block_cache() { static BlockCache* c = new BlockCache; return
 struct Quiesce { void (*fn)(void*); void* arg; bool done; };
 thread_local Quiesce* tl_quiesce = nullptr;
 
+// Waits for whatever may still read an owner's device memory before that memory is released or rewritten in place by the host
+// (a synchronous hipMemcpy does not wait for non-blocking streams): the streams of the context whose call is on the stack, once
+// per call, or the device
+void wait_for_readers()
+{
+    if (tl_quiesce) { if (!tl_quiesce->done) { tl_quiesce->fn(tl_quiesce->arg); tl_quiesce->done = true; } }
+    else (void)hipDeviceSynchronize();
+}
+
 struct DevBuf {                     // grow-only device allocation
     void* p = nullptr;
     size_t bytes = 0;
@@ -136,8 +145,7 @@ struct DevBuf {                     // grow-only device allocation
         int cur = -1;
         (void)hipGetDevice(&cur);
         if (cur != dev) (void)hipSetDevice(dev);
-        if (tl_quiesce) { if (!tl_quiesce->done) { tl_quiesce->fn(tl_quiesce->arg); tl_quiesce->done = true; } }
-        else (void)hipDeviceSynchronize();
+        wait_for_readers();
         static const bool no_cache = getenv("EFX_NO_BLOCK_CACHE") != nullptr;
         if (no_cache) (void)hipFree(p); else block_cache().give(p, bytes, dev);
         if (cur != dev && cur >= 0) (void)hipSetDevice(cur);
@@ -409,13 +417,14 @@ struct efx_context {
     bool hist_clean = false;        // the key histograms are zero (nms_kernel adds, select_kernel's leaders read and clear: they stay zero across frames
                                     // unless a call failed half-way or the buffer is new)
     DevBuf rplan; ResizePlanLevel rplan_lv[EFX_MAX_LEVELS];        // resize plan (tables of resize_stream_kernel)
-    RowsPlanLaunch rows_plan[EFX_MAX_LEVELS];                       // ... and of resize_rows_kernel, by source level
+    RowsPlanLaunch rows_plan[EFX_MAX_BATCH + 1][EFX_MAX_LEVELS];    // ... and of resize_rows_kernel, by frames per launch and source level
+    std::vector<unsigned char> h_table_bytes;                       // what d_table holds (build_geometry rewrites it only when this changes)
+    std::vector<unsigned char> h_rplan_bytes;                       // ... and what rplan holds
     DevBuf blurred;                 // blurred copies of the pyramid levels for the BAD describer (blur_levels_kernel), on first use
     hipStream_t side = nullptr;     // side stream + fork / join events of the level blur (DetectLaunch::blur_fork), on first use
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int idle_streak = 0;            // consecutive calls that found their stream idle (where the level blur runs: detect_common)
     int g_frames = 0;               // frames the per-frame buffers were reserved for (batched launches: detect_frames)
-    int g_plan_frames = 0;          // frames per launch the row-walking pyramid plan was chunked for (build_rows_plan)
     FrameStride fs = {};            // distance between the frames' copies inside the buffers (efx_device.h)
     int last_frames = 1;            // frames of the last detect call (the summary mirror reads the LAST one)
     Summary* h_mirror = nullptr;    // host copy of the last frame's summary, filled on demand by fetch_summary()
@@ -726,11 +735,33 @@ void build_rows_plan(const LevelTable& T, int nlevels, int nframes, std::vector<
     }
 }
 
-// pyramid geometry, quotas, caps (calcImagePyramid .cpp:136-157, calcNumFeaturesPerLevel :159-174, :252)
+// the parameters the geometry is made of (the threshold, the radius and the describer are kernel arguments)
+bool same_geometry_params(const efx_params& a, const efx_params& b)
+{
+    return a.nfeatures == b.nfeatures && memcmp(&a.scale_factor, &b.scale_factor, sizeof(float)) == 0 && a.nlevels == b.nlevels &&
+           a.first_level == b.first_level;
+}
+
+// Writes `bytes` to `dst` with a synchronous copy, unless `dst` already holds them (`held`, the host copy of its contents).  A
+// block that launches still queued on the context's streams may read (`dst` is where it was when `held` was written) is
+// rewritten only after those streams have drained: a synchronous hipMemcpy does not wait for non-blocking streams.
+hipError_t upload_table(DevBuf& dst, const void* held_at, std::vector<unsigned char>& held, const void* bytes, size_t n)
+{
+    if (dst.p == held_at && held.size() == n && memcmp(held.data(), bytes, n) == 0) return hipSuccess;
+    if (dst.p == held_at && !held.empty()) wait_for_readers();
+    held.clear();
+    const hipError_t e = hipMemcpy(dst.p, bytes, n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) held.assign(static_cast<const unsigned char*>(bytes), static_cast<const unsigned char*>(bytes) + n);
+    return e;
+}
+
+// pyramid geometry, quotas, caps (calcImagePyramid .cpp:136-157, calcNumFeaturesPerLevel :159-174, :252).  The geometry does not
+// depend on the frames per launch: a launch of another frame count on the same geometry only has to find its buffers large
+// enough, and writes nothing a queued launch could read (the rows plans of every frame count are built with the geometry).
 int build_geometry(efx_context* c, int rows, int cols, int nframes = 1)
 {
     const efx_params& p = c->p;
-    if (c->g_rows == rows && c->g_cols == cols && c->g_frames >= nframes && c->g_plan_frames == nframes && memcmp(&c->g_p, &p, sizeof(p)) == 0) return EFX_OK;
+    if (c->g_rows == rows && c->g_cols == cols && c->g_frames >= nframes && same_geometry_params(c->g_p, p)) return EFX_OK;
     const size_t NF = (size_t)std::max(nframes, c->g_rows == rows && c->g_cols == cols ? c->g_frames : 1);      // buffers never shrink
     LevelTable& T = c->h_table;
     memset(&T, 0, sizeof(T));
@@ -813,6 +844,7 @@ int build_geometry(efx_context* c, int rows, int cols, int nframes = 1)
     if (rows > 32767 || cols > 32767) return set_err(c->err, EFX_ERR_UNSUPPORTED, "image larger than 32767 (short2 coordinates)");
 
     // the level table is followed by one packed word per tile (efx_pack_tile / efx_tile_of)
+    const void* table_at = c->d_table.p;
     HIP_TRY(c->err, c->d_table.reserve(sizeof(LevelTable) + (size_t)(tiles + 1) * sizeof(uint32_t)));
     // everything below exists once per frame of a batched launch, `fs` apart
     c->fs.pyramid = align_up(pyr + 256, 256);
@@ -846,7 +878,8 @@ int build_geometry(efx_context* c, int rows, int cols, int nframes = 1)
         if (!c->h_mirror) return set_err(c->err, EFX_ERR_NOMEM, "out of host memory");
         memset(c->h_mirror, 0, sizeof(Summary));
     }
-    // synchronous upload: geometry changes are rare (first frame / size or parameter change)
+    // synchronous upload: geometry changes are rare (first frame / size or parameter change); launches still queued read the
+    // table they were enqueued with (upload_table waits for them before it rewrites the block)
     {
         std::vector<unsigned char> blob(sizeof(LevelTable) + (size_t)(tiles + 1) * sizeof(uint32_t), 0);
         memcpy(blob.data(), &T, sizeof(LevelTable));
@@ -856,7 +889,7 @@ int build_geometry(efx_context* c, int rows, int cols, int nframes = 1)
             for (int ty = 0; ty < L.tiles_y; ty++)
                 for (int tx = 0; tx < L.tiles_x; tx++) info[L.tile_base + ty * L.tiles_x + tx] = efx_pack_tile((uint32_t)s, (uint32_t)tx, (uint32_t)ty);
         }
-        HIP_TRY(c->err, hipMemcpy(c->d_table.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
+        HIP_TRY(c->err, upload_table(c->d_table, table_at, c->h_table_bytes, blob.data(), blob.size()));
     }
     // resize plan: per destination level the column / row / tile tables of resize_stream_kernel (spec S5 expressions)
     {
@@ -911,13 +944,38 @@ int build_geometry(efx_context* c, int rows, int cols, int nframes = 1)
                     if (ndw > 32 || nrow > 80) R.W = 0;          // footprint beyond what the streamed kernel stages: no plan
                 }
         }
-        build_rows_plan(T, p.nlevels, nframes, blob, c->rows_plan);
+        // the row-walking plan of every frame count a launch can have (its chunks depend on the frames per launch), each in a
+        // region of its own: a launch of another frame count on this geometry reads tables nothing rewrites.  Frame counts whose
+        // plans come out the same share a region.
+        std::vector<std::vector<int>> seg(EFX_MAX_BATCH + 1);
+        std::vector<RowsPlanLaunch> rel((size_t)(EFX_MAX_BATCH + 1) * EFX_MAX_LEVELS);
+        memset(c->rows_plan, 0, sizeof(c->rows_plan));
+        for (int f = 1; f <= EFX_MAX_BATCH; f++) {
+            RowsPlanLaunch* R = rel.data() + (size_t)f * EFX_MAX_LEVELS;         // offsets relative to seg[f]
+            build_rows_plan(T, p.nlevels, f, seg[f], R);
+            int same = 0;
+            for (int g = 1; g < f && !same; g++)
+                if (memcmp(rel.data() + (size_t)g * EFX_MAX_LEVELS, R, sizeof(RowsPlanLaunch) * EFX_MAX_LEVELS) == 0 && seg[g] == seg[f]) same = g;
+            if (same) { memcpy(c->rows_plan[f], c->rows_plan[same], sizeof(c->rows_plan[f])); continue; }
+            while (blob.size() & 3) blob.push_back(0);
+            const unsigned base = (unsigned)(blob.size() * 4);
+            blob.insert(blob.end(), seg[f].begin(), seg[f].end());
+            for (int s = 0; s < EFX_MAX_LEVELS; s++) {
+                RowsPlanLaunch L = R[s];
+                if (L.nlev > 0) {
+                    for (int k = 0; k < L.nlev; k++) { L.x_off[k] += base; L.y_off[k] += base; }
+                    L.strip_off += base; L.chunk_off += base;
+                }
+                c->rows_plan[f][s] = L;
+            }
+        }
         if (!blob.empty()) {
+            const void* plan_at = c->rplan.p;
             HIP_TRY(c->err, c->rplan.reserve(blob.size() * 4));
-            HIP_TRY(c->err, hipMemcpy(c->rplan.p, blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
+            HIP_TRY(c->err, upload_table(c->rplan, plan_at, c->h_rplan_bytes, blob.data(), blob.size() * 4));
         }
     }
-    c->g_rows = rows; c->g_cols = cols; c->g_p = p; c->g_frames = (int)NF; c->g_plan_frames = nframes;
+    c->g_rows = rows; c->g_cols = cols; c->g_p = p; c->g_frames = (int)NF;
     return EFX_OK;
 }
 
@@ -968,7 +1026,7 @@ int detect_frames(efx_context* c, int nframes, const uint8_t* const* d_images, i
     a.d_table = static_cast<const LevelTable*>(c->d_table.p);
     a.h_table = &c->h_table;
     a.hdr = static_cast<TileHdr*>(c->hdr.p);
-    a.rplan = static_cast<const unsigned char*>(c->rplan.p); a.rplan_lv = c->rplan_lv; a.rows_plan = c->rows_plan;
+    a.rplan = static_cast<const unsigned char*>(c->rplan.p); a.rplan_lv = c->rplan_lv; a.rows_plan = c->rows_plan[nframes];
     a.cand = static_cast<Corner*>(c->cand.p);
     a.surv = static_cast<Corner*>(c->surv.p);
     a.slots = static_cast<unsigned char*>(c->slots.p);
@@ -1305,16 +1363,17 @@ int efx_set_descriptor_type(efx_context* ctx, int v)
     if (rc) return rc;
     if (v == ctx->p.descriptor_type) return EFX_OK;
     ctx->p = q;
+    // describer_init rewrites the BAD boxes / HashSIFT weights in place when the new table fits the block: describes still queued
+    // on the context's streams read the old one, so they are waited for first (Quiesce, like any regrow)
+    Quiesce q2 = { &efx_context::quiesce_cb, ctx, false };
+    Quiesce* prev = tl_quiesce;
+    tl_quiesce = &q2;
+    wait_for_readers();
     rc = ctx_rebuild_describer(ctx);
     // the blurred copies of the levels (+103 MB at 8K) serve BAD describers only: a context switched to HashSIFT gives them back
-    // (ADVICE r4); its streams are waited for first, like any regrow (Quiesce)
-    if (rc == EFX_OK && ctx->desc.kind != 0 && ctx->blurred.p) {
-        Quiesce q2 = { &efx_context::quiesce_cb, ctx, false };
-        Quiesce* prev = tl_quiesce;
-        tl_quiesce = &q2;
-        ctx->blurred.release();
-        tl_quiesce = prev;
-    }
+    // 
+    if (rc == EFX_OK && ctx->desc.kind != 0 && ctx->blurred.p) ctx->blurred.release();
+    tl_quiesce = prev;
     return rc;
 }
 int efx_get_descriptor_type(const efx_context* ctx) { return ctx ? ctx->p.descriptor_type : -1; }
@@ -1360,7 +1419,9 @@ int efx_detect_and_compute_batch_async(efx_context* const* ctxs, void* const* st
                                        uint8_t* const* d_descriptors, size_t desc_pitch, int capacity, int* const* d_counts)
 {
     if (!ctxs || nctx <= 0 || nframes < 0 || !d_images || !d_keypoints || !d_counts) return EFX_ERR_BAD_ARG;
-    for (int j = 0; j < nctx && j < nframes; j++) if (!ctxs[j]) return EFX_ERR_BAD_ARG;
+    if (nframes == 0) return EFX_OK;
+    if (!ctxs[0]) return EFX_ERR_BAD_ARG;
+    for (int j = 1; j < nctx && j < nframes; j++) if (!ctxs[j]) return EFX_ERR_BAD_ARG;
     // Context j owns the frames j, j + nctx, j + 2 nctx, ...: they go through ONE launch of every kernel, EFX_MAX_BATCH at a time
     // (frame = blockIdx.y; detect_frames).  EFX_NO_BATCH=1: one single-frame call per frame, in frame order (the round-5 form).
     if (ctxs[0]->knobs.no_batch) {

@@ -11,6 +11,11 @@
  *   - a context is NOT re-entrant: one context per (thread, stream, device), exactly like an
  *     EfficientFeaturesImpl instance (cuda_efficient_features.cpp:391-403).  Parameter tables are
  *     per-context (the reference's process-global __constant__ tables, cuda_bad.cu:49-50, are not copied).
+ *     Calls on one context are ordered by their stream: setters, a new frame size, a new batch size or
+ *     another entry point between calls still queued on it are safe.  Where the device tables change
+ *     (frame size, nfeatures, scale factor, nlevels, first level, descriptor type) the host waits for the
+ *     context's streams before it rewrites them; a change of the frames per launch, of the FAST threshold
+ *     or of the NMS radius costs no host wait.
  *
  * Keypoint matrix layout ("5xN"), identical to the reference (cuda_efficient_features.h:32-37):
  *   row 0 LOCATION  short2 (x, y) bit-packed in 4 bytes      row 3 OCTAVE   int32

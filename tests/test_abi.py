@@ -57,3 +57,14 @@ def test_product_does_not_reference_oracle():
             if f.endswith((".py", ".cpp", ".hip", ".h", ".hpp", ".S")) or f == "Makefile":
                 text = open(os.path.join(dirpath, f), errors="replace").read()
                 assert "efxo_" not in text and "pyoracle" not in text and "efx_oracle" not in text, f
+
+
+def test_batch_entry_without_frames_and_without_context(cef):
+    """efx_detect_and_compute_batch_async: no frames is a no-op that touches no context (not even ctxs[0]); a frame whose
+    context is NULL is an argument error, not a crash.  Neither reaches the device."""
+    P = ctypes.c_void_p
+    lib = cef.lib()
+    ctxs = (P * 1)(None)
+    img, kps, cnt = (P * 1)(P(16)), (P * 1)(P(32)), (P * 1)(P(48))       # never dereferenced: the calls return before
+    assert lib.efx_detect_and_compute_batch_async(ctxs, None, 1, img, 0, 240, 320, 320, kps, 2000, None, 0, 500, cnt) == 0
+    assert lib.efx_detect_and_compute_batch_async(ctxs, None, 1, img, 1, 240, 320, 320, kps, 2000, None, 0, 500, cnt) == -1
