@@ -41,7 +41,7 @@ ABI_SYMBOLS = [
     "efx_describer_last_error", "efx_describer_compute_kp4_async", "efx_describer_compute_async",
     "efx_describer_compute", "efx_describer_hashsift_debug_async",
     "efx_matcher_create", "efx_matcher_destroy", "efx_matcher_last_error", "efx_match_knn2_async",
-    "efx_match_crosscheck_async",
+    "efx_match_crosscheck_async", "efx_match_mutual_async", "efx_match_mutual_batch_async",
     "efx_detect_and_compute_batch_async", "efx_detect_and_compute_masked_async", "efx_compute_provided_async", "efx_detect_and_compute_ex",
     "efx_ic_angles_async", "efx_ic_angles", "efx_descriptors_to_csv",
     "efx_cvt_gray_async", "efx_host_alloc", "efx_host_free", "efx_uploader_create", "efx_uploader_destroy",
@@ -141,6 +141,11 @@ def lib():
         for name in ("efx_match_knn2_async", "efx_match_crosscheck_async"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p]
+        L.efx_match_mutual_async.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                             C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.efx_match_mutual_batch_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
+                                                   C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]
         L.efx_detect_and_compute_batch_async.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t,
                                                          C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         L.efx_detect_and_compute_masked_async.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t,
@@ -744,6 +749,95 @@ class BFMatcher:
         self._check(lib().efx_match_crosscheck_async(self._h, q.data_ptr(), q.stride(0), q.shape[0], t.data_ptr(), t.stride(0),
                                                      t.shape[0], q.shape[1], m.data_ptr(), d.data_ptr(), _stream_ptr(stream)))
         return m[:q.shape[0]], d[:q.shape[0]]
+
+    @staticmethod
+    def _mdesc(t):
+        """_desc, accepting an empty (0-row) matrix whatever its strides: a count of 0 is a valid side of a mutual match."""
+        import torch
+        if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and t.shape[0] == 0 \
+                and t.shape[1] in (32, 64):
+            return t.contiguous()
+        return BFMatcher._desc(t)
+
+    @staticmethod
+    def _pitch(t):
+        return t.stride(0) if t.shape[0] > 0 else t.shape[1]
+
+    @staticmethod
+    def _count(c):
+        import torch
+        if c is None:
+            return None
+        if not (isinstance(c, torch.Tensor) and c.is_cuda and c.dtype == torch.int32 and c.numel() >= 1):
+            raise EfxError(-1, "a row count must be a 1-element int32 CUDA tensor (or None: the capacity)")
+        return c
+
+    def matchMutual(self, query, train, ratio=0.9, nq=None, nt=None, stream=None):
+        """The mutual ratio-test filter of samples/sample_image_sequence.cpp:114-137 on the device.  query / train:
+        capacity x 32|64 uint8 CUDA tensors; nq / nt: optional 1-element int32 CUDA tensors holding the row counts (read on the
+        device: no host sync), None = every row.  Returns (matches, nmatches): a q_capacity x 3 int32 tensor of {queryIdx,
+        trainIdx, distance} rows in ascending queryIdx, valid below nmatches[0] (a 1-element int32 tensor)."""
+        import torch
+        q, t = self._mdesc(query), self._mdesc(train)
+        if q.shape[1] != t.shape[1]:
+            raise EfxError(-1, "query and train descriptors differ in size")
+        cq, ct = self._count(nq), self._count(nt)
+        out = torch.empty((max(q.shape[0], 1), 3), dtype=torch.int32, device=q.device)
+        n = torch.empty((1,), dtype=torch.int32, device=q.device)
+        self._check(lib().efx_match_mutual_async(self._h, q.data_ptr(), self._pitch(q), cq.data_ptr() if cq is not None else None,
+                                                 q.shape[0], t.data_ptr(), self._pitch(t), ct.data_ptr() if ct is not None else None,
+                                                 t.shape[0], q.shape[1], float(ratio), out.data_ptr(), n.data_ptr(),
+                                                 _stream_ptr(stream)))
+        return out[:q.shape[0]], n
+
+    def matchMutualBatch(self, queries, trains, ratio=0.9, nqs=None, nts=None, stream=None):
+        """matchMutual over npairs pairs in one call (MutualBatch, run once): lists of (matches, nmatches)."""
+        b = MutualBatch(self, queries, trains, ratio, nqs, nts, stream)
+        b.run()
+        return b.matches, b.nmatches
+
+
+class MutualBatch:
+    """efx_match_mutual_batch_async with prepared pointer tables (like Batch): pair i matches queries[i] against trains[i], with
+    optional device counts nqs[i] / nts[i]; every query matrix has one shape and pitch, every train matrix too.  The outputs are
+    allocated here (matches[i]: q_capacity x 3 int32, nmatches[i]: 1 int32); run() crosses the ABI once and may be repeated."""
+
+    def __init__(self, matcher, queries, trains, ratio=0.9, nqs=None, nts=None, stream=None):
+        import torch
+        n = len(queries)
+        if len(trains) != n or (nqs is not None and len(nqs) != n) or (nts is not None and len(nts) != n):
+            raise EfxError(-1, "one train matrix (and count) per query matrix")
+        qs = [BFMatcher._mdesc(q) for q in queries]
+        ts = [BFMatcher._mdesc(t) for t in trains]
+        for a in qs + ts:
+            if a.shape[1] != qs[0].shape[1]:
+                raise EfxError(-1, "every descriptor matrix of a batch has one row size")
+        for group in (qs, ts):
+            for a in group:
+                if a.shape[0] != group[0].shape[0] or BFMatcher._pitch(a) != BFMatcher._pitch(group[0]):
+                    raise EfxError(-1, "the query (train) matrices of a batch have one capacity and pitch")
+        cq = [BFMatcher._count(c) for c in nqs] if nqs is not None else None
+        ct = [BFMatcher._count(c) for c in nts] if nts is not None else None
+        qcap = qs[0].shape[0] if n else 0
+        dev = qs[0].device if n else None
+        self.matches = [torch.empty((max(qcap, 1), 3), dtype=torch.int32, device=dev)[:qcap] for _ in range(n)]
+        self.nmatches = [torch.empty((1,), dtype=torch.int32, device=dev) for _ in range(n)]
+        self._keep = (matcher, qs, ts, cq, ct, stream)
+        P = C.c_void_p
+        self._q = (P * max(n, 1))(*[P(a.data_ptr()) for a in qs])
+        self._t = (P * max(n, 1))(*[P(a.data_ptr()) for a in ts])
+        self._nq = (P * max(n, 1))(*[P(c.data_ptr()) if c is not None else P() for c in cq]) if cq is not None else None
+        self._nt = (P * max(n, 1))(*[P(c.data_ptr()) if c is not None else P() for c in ct]) if ct is not None else None
+        self._m = (P * max(n, 1))(*[P(a.data_ptr()) for a in self.matches])
+        self._n = (P * max(n, 1))(*[P(a.data_ptr()) for a in self.nmatches])
+        self._args = (n, BFMatcher._pitch(qs[0]) if n else 32, qcap, BFMatcher._pitch(ts[0]) if n else 32, ts[0].shape[0] if n else 0,
+                      qs[0].shape[1] if n else 32, float(ratio))
+
+    def run(self):
+        matcher, stream = self._keep[0], self._keep[5]
+        n, qp, qcap, tp, tcap, db, ratio = self._args
+        matcher._check(lib().efx_match_mutual_batch_async(matcher._h, n, self._q, qp, self._nq, qcap, self._t, tp, self._nt, tcap,
+                                                          db, ratio, self._m, self._n, _stream_ptr(stream)))
 
 
 def unpack_keypoints(kps):

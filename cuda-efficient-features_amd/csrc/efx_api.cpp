@@ -10,6 +10,13 @@
 
 // match_kernels.hip (declared here, not in efx_device.h: that header is one of the headline kernels' stamped sources, profiles/rNN_counters.json)
 int efx_knn2_mfma_resident_workgroups(int desc_bytes, int fp4);
+size_t efx_mutual_expanded_row(int desc_bytes, int fp4);
+hipError_t efx_launch_mutual_expand(int nmat, const uint8_t* const* src, const size_t* pitch, const int* const* n, const int* cap,
+                                    int cap_max, int desc_bytes, int fp4, uint8_t* const* dst, hipStream_t stream);
+hipError_t efx_launch_mutual(int npairs, const uint8_t* const* q, const uint8_t* const* t, const int* const* nq, const int* const* nt,
+                             size_t q_pitch, size_t t_pitch, int q_cap, int t_cap, int desc_bytes, double ratio,
+                             int* const* out, int* const* nout, int path, int nchunks,
+                             void* partial, void* knn, void* flags, void* wgcount, hipStream_t stream);
 
 #include <math.h>
 #include <stdarg.h>
@@ -21,6 +28,7 @@ int efx_knn2_mfma_resident_workgroups(int desc_bytes, int fp4);
 #include <algorithm>
 #include <string>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 // learned parameter blobs, embedded by params_embed.S
@@ -398,8 +406,13 @@ struct efx_matcher {
     bool no_mfma = getenv("EFX_MATCH_NO_MFMA") != nullptr;        // variant knob (tests: force the popcount kernel), read when the matcher is created
     bool no_fp4 = getenv("EFX_MATCH_NO_FP4") != nullptr;          // ... the int8 matrix-core kernel instead of the FP4 one
     DevBuf scratch, expanded, a_idx, a_dist, b_idx, b_dist;
+    DevBuf mx, mpart, mknn, mflag;  // mutual matching: expanded matrices, per-chunk best two, best-two lists, flags + workgroup counts
     std::string err;
-    ~efx_matcher() { scratch.release(); expanded.release(); a_idx.release(); a_dist.release(); b_idx.release(); b_dist.release(); }
+    ~efx_matcher()
+    {
+        scratch.release(); expanded.release(); a_idx.release(); a_dist.release(); b_idx.release(); b_dist.release();
+        mx.release(); mpart.release(); mknn.release(); mflag.release();
+    }
 };
 
 struct efx_context {
@@ -2072,6 +2085,140 @@ int efx_match_crosscheck_async(efx_matcher* m, const uint8_t* d_query, size_t q_
         HIP_TRY(m->err, hipMemcpy2DAsync(d_dist, 4, m->a_dist.p, 8, 4, (size_t)nq, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     }
     return EFX_OK;
+}
+
+// ---- mutual ratio-test matching on device counts ----
+// Train chunks per job of the matrix-core search: the (query block, chunk) workgroups of all jobs of a launch run in
+// ceil(workgroups / resident) rounds, each workgroup over ceil(tiles / chunks) tiles plus a fixed cost of about two tiles
+// (query fragments, partial rows); the count with the least rounds x work wins, fewer chunks on ties.  For ONE job this picks
+// knn2_run's single round (40 000 x 40 000: three chunks).
+static int mutual_mfma_chunks(int resident, int njobs, int cap)
+{
+    const long qblocks = (long)njobs * ((cap + 255) / 256);
+    const int ntiles = (cap + 31) / 32;
+    int best = 1; long best_cost = -1;
+    for (int c = 1; c <= 64 && c <= (ntiles > 0 ? ntiles : 1); c++) {
+        const long rounds = (qblocks * c + resident - 1) / resident;
+        const long cost = rounds * ((ntiles + c - 1) / c + 2);
+        if (best_cost < 0 || cost < best_cost) { best = c; best_cost = cost; }
+    }
+    return best;
+}
+
+int efx_match_mutual_batch_async(efx_matcher* m, int npairs,
+                                 const uint8_t* const* d_query, size_t q_pitch, const int* const* d_nq, int q_capacity,
+                                 const uint8_t* const* d_train, size_t t_pitch, const int* const* d_nt, int t_capacity,
+                                 int desc_bytes, double ratio, int* const* d_matches, int* const* d_nmatches, void* stream)
+{
+    if (!m) return EFX_ERR_BAD_ARG;
+    if (npairs < 0) return set_err(m->err, EFX_ERR_BAD_ARG, "negative pair count");
+    if (npairs == 0) return EFX_OK;
+    const int db = desc_bytes;
+    if (db != 32 && db != 64) return set_err(m->err, EFX_ERR_BAD_ARG, "descriptor size must be 32 or 64 bytes");
+    if (q_capacity < 0 || t_capacity < 0) return set_err(m->err, EFX_ERR_BAD_ARG, "negative capacity");
+    if (!d_query || !d_train || !d_matches || !d_nmatches) return set_err(m->err, EFX_ERR_BAD_ARG, "null pointer table");
+    if (q_pitch < (size_t)db || t_pitch < (size_t)db || ((q_pitch | t_pitch) & 3u))
+        return set_err(m->err, EFX_ERR_BAD_ARG, "descriptor rows must be 4-byte aligned and at least desc_bytes apart");
+    for (int p = 0; p < npairs; p++) {
+        if ((q_capacity > 0 && !d_query[p]) || (t_capacity > 0 && !d_train[p])) return set_err(m->err, EFX_ERR_BAD_ARG, "null descriptors");
+        if (((uintptr_t)d_query[p] | (uintptr_t)d_train[p]) & 3u) return set_err(m->err, EFX_ERR_BAD_ARG, "descriptor rows must be 4-byte aligned");
+        if (!d_matches[p] || !d_nmatches[p]) return set_err(m->err, EFX_ERR_BAD_ARG, "null outputs");
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    // matrix cores when both directions qualify (knn2_run's rule, on capacities); the popcount kernel otherwise
+    const int path = (!m->no_mfma && q_capacity >= 128 && t_capacity >= 128) ? (m->no_fp4 ? 1 : 2) : 0;
+    const int cap = std::max(q_capacity, t_capacity);
+    const int chain = std::min(npairs, EFX_MAX_BATCH);     // pairs of the largest launch chain
+    const int njobs = 2 * chain;
+    int nchunks;
+    if (path) nchunks = mutual_mfma_chunks(efx_knn2_mfma_resident_workgroups(db, path == 2 ? 1 : 0), njobs, cap);
+    else nchunks = std::max(1, std::min(std::min(64, std::max(cap, 1)), 1024 / (njobs * std::max(1, (cap + 255) / 256))));
+
+    // Expanded matrices live in slots planned per chain: a chain's distinct matrices (rows, pitch, count pointer, capacity) take
+    // one slot each and are expanded once, then serve as the query operand of one direction and the train operand of the other in
+    // every pair of the chain they appear in.  A matrix the previous chain left in a slot (frame i of pairs i - 1 and i across a
+    // chain boundary) keeps it and is not expanded again.  A new slot is opened only when every slot holds a matrix the chain
+    // reads, so there are at most 2 * EFX_MAX_BATCH slots: the scratch is bounded by a chain, not by the call.  A chain's
+    // expansions overwrite only slots it does not read, and run after the previous chain's kernels (one stream).
+    struct Mat { const uint8_t* src; size_t pitch; const int* n; int cap; };
+    auto same = [](const Mat& x, const Mat& y) { return x.src == y.src && x.pitch == y.pitch && x.n == y.n && x.cap == y.cap; };
+    std::vector<Mat> slot;                                 // the matrix each slot holds
+    std::vector<int> qs(npairs, -1), ts(npairs, -1);       // slot of each pair's query / train matrix
+    // what each chain expands, and where (recorded here: a later chain may refill the slot before the launches are issued)
+    std::vector<std::vector<std::pair<int, Mat>>> fresh((npairs + EFX_MAX_BATCH - 1) / EFX_MAX_BATCH);
+    if (path) {
+        for (int c = 0, p0 = 0; p0 < npairs; c++, p0 += EFX_MAX_BATCH) {
+            const int k = std::min(npairs - p0, EFX_MAX_BATCH);
+            std::vector<char> used(slot.size(), 0);         // slots this chain reads
+            auto find = [&](const Mat& M) { for (size_t i = 0; i < slot.size(); i++) if (same(slot[i], M)) return (int)i; return -1; };
+            for (int p = p0; p < p0 + k; p++) {             // carried over from the previous chain
+                const int a = find({ d_query[p], q_pitch, d_nq ? d_nq[p] : nullptr, q_capacity });
+                const int b = find({ d_train[p], t_pitch, d_nt ? d_nt[p] : nullptr, t_capacity });
+                if (a >= 0) { qs[p] = a; used[a] = 1; }
+                if (b >= 0) { ts[p] = b; used[b] = 1; }
+            }
+            auto place = [&](const Mat& M) {                // a slot nobody in this chain reads, or a new one
+                int i = find(M);
+                if (i >= 0 && used[i]) return i;
+                for (i = 0; i < (int)slot.size() && used[i]; i++) {}
+                if (i == (int)slot.size()) { slot.push_back(M); used.push_back(0); } else slot[i] = M;
+                used[i] = 1;
+                fresh[c].push_back({ i, M });
+                return i;
+            };
+            for (int p = p0; p < p0 + k; p++) {
+                if (qs[p] < 0) qs[p] = place({ d_query[p], q_pitch, d_nq ? d_nq[p] : nullptr, q_capacity });
+                if (ts[p] < 0) ts[p] = place({ d_train[p], t_pitch, d_nt ? d_nt[p] : nullptr, t_capacity });
+            }
+        }
+    }
+    const size_t rows_pad = (size_t)((cap + 255) & ~255);
+    const size_t xrow = rows_pad * efx_mutual_expanded_row(db, path == 2 ? 1 : 0);
+    const int nblk = std::max(1, (q_capacity + 255) / 256);
+    const size_t flag_bytes = align_up((size_t)chain * (size_t)std::max(q_capacity, 1), 256);
+    // every block is reserved before the first launch: a regrow (the only place this path may wait on the host) never finds
+    // work of THIS call in flight
+    HIP_TRY(m->err, m->mx.reserve(std::max<size_t>(slot.size() * xrow, 1)));
+    HIP_TRY(m->err, m->mpart.reserve((size_t)njobs * nchunks * std::max(cap, 1) * 16));
+    HIP_TRY(m->err, m->mknn.reserve((size_t)njobs * std::max(cap, 1) * 16));
+    HIP_TRY(m->err, m->mflag.reserve(flag_bytes + (size_t)chain * nblk * 4));
+    uint8_t* const xbase = static_cast<uint8_t*>(m->mx.p);
+    const int fp4 = path == 2 ? 1 : 0;
+    for (int c = 0, p0 = 0; p0 < npairs; c++, p0 += EFX_MAX_BATCH) {
+        const int k = std::min(npairs - p0, EFX_MAX_BATCH);
+        if (path) {                                         // the chain's new matrices: one launch (at most 2 * EFX_MAX_BATCH)
+            const int nf = (int)fresh[c].size();
+            const uint8_t* src[2 * EFX_MAX_BATCH]; size_t pitch[2 * EFX_MAX_BATCH]; const int* n[2 * EFX_MAX_BATCH];
+            int cp[2 * EFX_MAX_BATCH]; uint8_t* dst[2 * EFX_MAX_BATCH];
+            for (int i = 0; i < nf; i++) {
+                const Mat& M = fresh[c][i].second;
+                src[i] = M.src; pitch[i] = M.pitch; n[i] = M.n; cp[i] = M.cap; dst[i] = xbase + (size_t)fresh[c][i].first * xrow;
+            }
+            hipError_t e = efx_launch_mutual_expand(nf, src, pitch, n, cp, cap, db, fp4, dst, st);
+            if (e != hipSuccess) return set_err(m->err, EFX_ERR_HIP, "expansion launch failed: %s", hipGetErrorString(e));
+        }
+        const uint8_t* q[EFX_MAX_BATCH]; const uint8_t* t[EFX_MAX_BATCH]; const int* nq[EFX_MAX_BATCH]; const int* nt[EFX_MAX_BATCH];
+        for (int i = 0; i < k; i++) {
+            const int p = p0 + i;
+            q[i] = path ? xbase + (size_t)qs[p] * xrow : d_query[p];
+            t[i] = path ? xbase + (size_t)ts[p] * xrow : d_train[p];
+            nq[i] = d_nq ? d_nq[p] : nullptr; nt[i] = d_nt ? d_nt[p] : nullptr;
+        }
+        const size_t xp = efx_mutual_expanded_row(db, fp4);
+        hipError_t e = efx_launch_mutual(k, q, t, nq, nt, path ? xp : q_pitch, path ? xp : t_pitch, q_capacity, t_capacity, db, ratio,
+                                         d_matches + p0, d_nmatches + p0, path, nchunks, m->mpart.p, m->mknn.p, m->mflag.p,
+                                         static_cast<uint8_t*>(m->mflag.p) + flag_bytes, st);
+        if (e != hipSuccess) return set_err(m->err, EFX_ERR_HIP, "mutual match launch failed: %s", hipGetErrorString(e));
+    }
+    return EFX_OK;
+}
+
+int efx_match_mutual_async(efx_matcher* m, const uint8_t* d_query, size_t q_pitch, const int* d_nq, int q_capacity,
+                           const uint8_t* d_train, size_t t_pitch, const int* d_nt, int t_capacity,
+                           int desc_bytes, double ratio, int* d_matches, int* d_nmatches, void* stream)
+{
+    return efx_match_mutual_batch_async(m, 1, &d_query, q_pitch, &d_nq, q_capacity, &d_train, t_pitch, &d_nt, t_capacity, desc_bytes,
+                                        ratio, &d_matches, &d_nmatches, stream);
 }
 
 int efx_level_geometry(const efx_context* ctx, int rows, int cols, int level, int* lrows, int* lcols, float* scale)

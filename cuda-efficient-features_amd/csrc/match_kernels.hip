@@ -455,6 +455,316 @@ __global__ void crosscheck_kernel(const int* __restrict__ q2t, const int* __rest
     match[qi] = (j >= 0 && t2q[2 * j] == qi) ? j : -1;
 }
 
+// ================================================================================================
+// Mutual ratio-test matching on DEVICE row counts (efx_match_mutual_async / efx_match_mutual_batch_async): the
+// filter of samples/sample_image_sequence.cpp:114-137 without a host round trip.  One launch of each kernel serves a chain of up
+// to EFX_MAX_BATCH pairs: job z = blockIdx.z is pair z >> 1 in direction z & 1 (0: query -> train, 1: train -> query).  Row counts
+// are read at kernel start from device ints (one scalar load; NULL: the capacity), grids and scratch are sized from the
+// capacities, and workgroups past a count exit at once.  The host-count kernels above keep their code generation: these are
+// separate kernels (the matrix-core one restates knn2_mfma_kernel's loop for one 32-query block per wave).
+// ================================================================================================
+struct MutualJobs {                      // a chain's pairs, passed by value (kernel arguments: no table upload, nothing to race)
+    const uint8_t* q[EFX_MAX_BATCH];     // query rows of pair p: raw descriptors (popcount path) or expanded rows (matrix cores)
+    const uint8_t* t[EFX_MAX_BATCH];     // train rows of pair p
+    const int* nq[EFX_MAX_BATCH];        // device counts (NULL: the capacity), clamped to [0, capacity]
+    const int* nt[EFX_MAX_BATCH];
+    int* out[EFX_MAX_BATCH];             // d_matches (3 ints per row) and d_nmatches of pair p
+    int* nout[EFX_MAX_BATCH];
+    size_t q_pitch, t_pitch;             // row pitches of the raw rows (expanded rows are dense)
+    int q_cap, t_cap, cap;               // capacities; cap = the larger: row stride of the partial and best-two lists
+    int nchunks;                         // train chunks per job (grid.y)
+};
+
+__device__ __forceinline__ int mutual_count(const int* p, int cap)
+{
+    if (!p) return cap;
+    const int n = *p;
+    return n < 0 ? 0 : (n > cap ? cap : n);
+}
+
+// the operands of job z: queries (rows, pitch, count) and trains
+struct MutualJob { const uint8_t* q; const uint8_t* t; size_t qp, tp; int nq, nt; };
+__device__ __forceinline__ MutualJob mutual_job(const MutualJobs& J, int z)
+{
+    const int p = z >> 1;
+    const int na = mutual_count(J.nq[p], J.q_cap), nb = mutual_count(J.nt[p], J.t_cap);
+    MutualJob j;
+    if (z & 1) { j.q = J.t[p]; j.t = J.q[p]; j.qp = J.t_pitch; j.tp = J.q_pitch; j.nq = nb; j.nt = na; }
+    else { j.q = J.q[p]; j.t = J.t[p]; j.qp = J.q_pitch; j.tp = J.t_pitch; j.nq = na; j.nt = nb; }
+    return j;
+}
+
+struct ExpandJobs {                      // the distinct descriptor matrices of one expansion launch (matrix = blockIdx.z)
+    const uint8_t* src[2 * EFX_MAX_BATCH];
+    const int* n[2 * EFX_MAX_BATCH];
+    size_t pitch[2 * EFX_MAX_BATCH];
+    uint8_t* dst[2 * EFX_MAX_BATCH];     // its slot: round_up(capacity of the call, 256) expanded rows
+    int cap[2 * EFX_MAX_BATCH];
+};
+
+// expand_pm1_kernel / expand_fp4_kernel on device counts: matrix z -> its slot E.dst[z]; rows [0, n) expanded, [n, n rounded up
+// to 256) zero (a query block reads whole 256-row blocks, a train step whole 32-row tiles), the rest is never read and not written.
+// ONE expansion serves a matrix as the query operand of one direction and the train operand of the other (the layouts agree).
+template <bool FP4>
+__global__ __launch_bounds__(256) void expand_dc_kernel(ExpandJobs E, int nbytes)
+{
+    const int z = blockIdx.z;
+    const int n = mutual_count(E.n[z], E.cap[z]);
+    const int groups = nbytes >> 1;                        // 16 bits per thread
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)((n + 255) & ~255) * groups) return;
+    const int row = (int)(i / groups), g = (int)(i - (size_t)row * groups);
+    uint8_t* __restrict__ d = E.dst[z];
+    const uint8_t* p = E.src[z] + (size_t)row * E.pitch[z] + 2 * g;
+    if constexpr (FP4) {
+        uint2 out = make_uint2(0u, 0u);
+        if (row < n) {
+            uint32_t w[2];
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                uint32_t x = p[k];                          // bit j -> bit 4 j (expand_fp4_kernel)
+                x = (x | (x << 12)) & 0x000f000fu;
+                x = (x | (x << 6)) & 0x03030303u;
+                x = (x | (x << 3)) & 0x11111111u;
+                w[k] = 0x22222222u | ((~x & 0x11111111u) << 3);
+            }
+            out = make_uint2(w[0], w[1]);
+        }
+        *reinterpret_cast<uint2*>(d + ((size_t)row * groups + g) * 8) = out;
+    } else {
+        uint4 out = make_uint4(0u, 0u, 0u, 0u);
+        if (row < n) {
+            const uint32_t bits = (uint32_t)p[0] | ((uint32_t)p[1] << 8);
+            uint32_t w[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const uint32_t ones = (((bits >> (4 * k)) & 15u) * 0x00204081u) & 0x01010101u;   // (expand_pm1_kernel)
+                w[k] = ones | ((ones ^ 0x01010101u) * 0xffu);
+            }
+            out = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+        *reinterpret_cast<uint4*>(d + ((size_t)row * groups + g) * 16) = out;
+    }
+}
+
+// knn2_kernel on device counts: the trains of job z in nchunks chunks of ceil(nt / nchunks)
+template <int NW>
+__global__ __launch_bounds__(256) void knn2_dc_kernel(MutualJobs J, Best2* __restrict__ partial)
+{
+    const int z = blockIdx.z;
+    const MutualJob j = mutual_job(J, z);
+    if ((int)blockIdx.x * 256 >= j.nq) return;
+    const int qi = blockIdx.x * 256 + threadIdx.x;
+    const int chunk = (j.nt + J.nchunks - 1) / J.nchunks;
+    const int t0 = blockIdx.y * chunk, t1 = min(t0 + chunk, j.nt);
+    uint32_t q[NW];
+    const uint32_t* qp = reinterpret_cast<const uint32_t*>(j.q + (size_t)min(qi, j.nq - 1) * j.qp);
+#pragma unroll
+    for (int k = 0; k < NW; k++) q[k] = qp[k];
+    Best2 b; b.d0 = 0x7fffffff; b.i0 = -1; b.d1 = 0x7fffffff; b.i1 = -1;
+    for (int t = t0; t < t1; t++) {
+        const uint32_t* tp = reinterpret_cast<const uint32_t*>(j.t + (size_t)t * j.tp);   // wave-uniform
+        int d = 0;
+#pragma unroll
+        for (int k = 0; k < NW; k++) d += __popc(q[k] ^ tp[k]);
+        if (d < b.d0) { b.d1 = b.d0; b.i1 = b.i0; b.d0 = d; b.i0 = t; }
+        else if (d < b.d1) { b.d1 = d; b.i1 = t; }
+    }
+    if (qi < j.nq) partial[((size_t)z * J.nchunks + blockIdx.y) * J.cap + qi] = b;
+}
+
+// knn2_mfma_kernel (CB = 1, eight waves) on device counts; FP4 / int8 operands, DB: the double-buffered train tile
+template <int NBITS, bool FP4, bool DB>
+__global__ __launch_bounds__(512) void knn2_mfma_dc_kernel(MutualJobs J, Best2* __restrict__ partial)
+{
+    constexpr int NT = 512;
+    constexpr int NB = FP4 ? NBITS / 2 : NBITS;
+    constexpr int KS = NB / 32;
+    constexpr int LP = NB + 16;
+    constexpr int NPIECE = 32 * NB / 16;
+    constexpr int NPF = (NPIECE + NT - 1) / NT;
+    typedef typename std::conditional<FP4, float, int>::type acc_t;
+    typedef typename std::conditional<FP4, f32x16, i32x16>::type accv_t;
+    const int LOWEST = FP4 ? 0 : -0x7fffffff;
+    __shared__ __attribute__((aligned(16))) uint8_t s_tiles[(DB ? 2 : 1) * 32 * LP];
+    const MutualJob j = mutual_job(J, blockIdx.z);
+    const int nq = j.nq, nt = j.nt;
+    if ((int)blockIdx.x * 256 >= nq) return;               // a workgroup past the count (uniform: before any barrier)
+    const uint8_t* __restrict__ xq = j.q;
+    const uint8_t* __restrict__ xt = j.t;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 31, lh = lane >> 5;
+    const int q0 = blockIdx.x * 256 + wave * 32;
+    i32x4 bq[KS];
+    {
+        const i32x4* p = reinterpret_cast<const i32x4*>(xq + (size_t)(q0 + li) * NB + 16 * lh);
+#pragma unroll
+        for (int ks = 0; ks < KS; ks++) bq[ks] = p[2 * ks];
+    }
+    const int ntiles = (nt + 31) >> 5;
+    const int tiles_per_chunk = (ntiles + J.nchunks - 1) / J.nchunks;
+    const int tile0 = blockIdx.y * tiles_per_chunk, tile1 = min(tile0 + tiles_per_chunk, ntiles);
+    int bd0 = LOWEST, bd1 = LOWEST, bi0 = -1, bi1 = -1;
+    uint4 pf[NPF];
+    auto fetch = [&](int tile) {
+        const uint4* src = reinterpret_cast<const uint4*>(xt + (size_t)tile * 32 * NB);
+#pragma unroll
+        for (int k = 0; k < NPF; k++) if (NPIECE % NT == 0 || tid + NT * k < NPIECE) pf[k] = src[tid + NT * k];
+    };
+    if (tile0 < tile1) fetch(tile0);
+    for (int tile = tile0; tile < tile1; tile++) {
+        uint8_t* s_tile = s_tiles + (DB ? ((tile - tile0) & 1) * 32 * LP : 0);
+#pragma unroll
+        for (int k = 0; k < NPF; k++) {
+            const int piece = tid + NT * k, row = piece / (NB / 16), col = piece - row * (NB / 16);
+            if (NPIECE % NT == 0 || piece < NPIECE) *reinterpret_cast<uint4*>(s_tile + row * LP + 16 * col) = pf[k];
+        }
+        __syncthreads();
+        if (tile + 1 < tile1) fetch(tile + 1);
+        accv_t acc;
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[r] = FP4 ? (acc_t)KNN_FP4_BIAS : (acc_t)0;
+        const uint8_t* arow = s_tile + li * LP + 16 * lh;
+        if constexpr (FP4) {
+            i32x4 af[KS];                                  // every fragment up front, the MFMAs as they arrive (knn2_mfma_kernel)
+#pragma unroll
+            for (int ks = 0; ks < KS; ks++) af[ks] = *reinterpret_cast<const i32x4*>(arow + 32 * ks);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int ks = 0; ks < KS; ks++) {
+                const i32x8 a8 = { af[ks][0], af[ks][1], af[ks][2], af[ks][3], 0, 0, 0, 0 };
+                const i32x8 b8 = { bq[ks][0], bq[ks][1], bq[ks][2], bq[ks][3], 0, 0, 0, 0 };
+                acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, acc, 4, 4, 0, 0, 0, 0);
+            }
+        } else {
+            i32x4 a = *reinterpret_cast<const i32x4*>(arow);
+#pragma unroll
+            for (int ks = 0; ks < KS; ks++) {
+                const i32x4 an = *reinterpret_cast<const i32x4*>(arow + 32 * (ks + 1 < KS ? ks + 1 : ks));
+                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bq[ks], acc, 0, 0, 0);
+                a = an;
+            }
+        }
+        const int t0 = tile * 32 + 4 * lh;
+        int key[16];
+#pragma unroll
+        for (int r = 0; r < 16; r++) key[r] = knn_key(acc[r]);
+        if (tile * 32 + 32 > nt) {                         // trains past the count must not compete
+#pragma unroll
+            for (int r = 0; r < 16; r++) if (t0 + (r & 3) + 8 * (r >> 2) >= nt) key[r] = LOWEST;
+        }
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const int m = knn_max4(key[4 * g], key[4 * g + 1], key[4 * g + 2], key[4 * g + 3]);
+            if (__builtin_expect(__ballot(m > bd1) == 0ull, 1)) continue;
+#pragma unroll
+            for (int r = 4 * g; r < 4 * g + 4; r++) {
+                const int d = key[r];
+                if (__ballot(d > bd1) == 0ull) continue;
+                const int ti = t0 + (r & 3) + 8 * (r >> 2);
+                if (d > bd0) { bd1 = bd0; bi1 = bi0; bd0 = d; bi0 = ti; }
+                else if (d > bd1) { bd1 = d; bi1 = ti; }
+            }
+        }
+        if (!DB) __syncthreads();
+    }
+    const int od0 = __shfl_xor(bd0, 32, 64), od1 = __shfl_xor(bd1, 32, 64);
+    const int oi0 = __shfl_xor(bi0, 32, 64), oi1 = __shfl_xor(bi1, 32, 64);
+    int d0 = bd0, d1 = bd1, i0 = bi0, i1 = bi1;
+    const int cd[2] = { od0, od1 }; const int ci[2] = { oi0, oi1 };
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        if (ci[k] < 0) continue;
+        if (i0 < 0 || knn_better(cd[k], ci[k], d0, i0)) { d1 = d0; i1 = i0; d0 = cd[k]; i0 = ci[k]; }
+        else if (i1 < 0 || knn_better(cd[k], ci[k], d1, i1)) { d1 = cd[k]; i1 = ci[k]; }
+    }
+    const int q = q0 + li;
+    if (lh == 0 && q < nq) {
+        auto dot_of = [](int key) -> int { return FP4 ? (int)(__builtin_bit_cast(float, key) - KNN_FP4_BIAS) : key; };
+        Best2 b;
+        b.d0 = i0 >= 0 ? (NBITS - dot_of(d0)) >> 1 : 0x7fffffff; b.i0 = i0;
+        b.d1 = i1 >= 0 ? (NBITS - dot_of(d1)) >> 1 : 0x7fffffff; b.i1 = i1;
+        partial[((size_t)blockIdx.z * J.nchunks + blockIdx.y) * J.cap + q] = b;
+    }
+}
+
+// knn2_merge_kernel on device counts: job z's best two per query -> knn[z * cap + query]
+__global__ __launch_bounds__(256) void knn2_merge_dc_kernel(MutualJobs J, const Best2* __restrict__ partial, Best2* __restrict__ knn)
+{
+    const int z = blockIdx.z;
+    const MutualJob j = mutual_job(J, z);
+    const int qi = blockIdx.x * 256 + threadIdx.x;
+    if (qi >= j.nq) return;
+    Best2 b; b.d0 = 0x7fffffff; b.i0 = -1; b.d1 = 0x7fffffff; b.i1 = -1;
+    for (int c = 0; c < J.nchunks; c++) {                  // train order: a strict `<` keeps the lower index on ties
+        const Best2 p = partial[((size_t)z * J.nchunks + c) * J.cap + qi];
+        const int cd[2] = { p.d0, p.d1 }, ci[2] = { p.i0, p.i1 };
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            if (ci[k] < 0) continue;
+            if (cd[k] < b.d0) { b.d1 = b.d0; b.i1 = b.i0; b.d0 = cd[k]; b.i0 = ci[k]; }
+            else if (cd[k] < b.d1) { b.d1 = cd[k]; b.i1 = ci[k]; }
+        }
+    }
+    knn[(size_t)z * J.cap + qi] = b;
+}
+
+// the sample's three checks for query i of pair p (a ratio test passes when the second neighbour is missing: S15)
+__device__ __forceinline__ bool mutual_keep(const Best2* __restrict__ knn, const MutualJobs& J, int p, int i, double ratio)
+{
+    const Best2 a = knn[(size_t)(2 * p) * J.cap + i];
+    if (a.i0 < 0) return false;                            // no train row
+    const Best2 b = knn[(size_t)(2 * p + 1) * J.cap + a.i0];
+    return b.i0 == i && !(a.i1 >= 0 && (double)a.d0 > ratio * (double)a.d1) && !(b.i1 >= 0 && (double)b.d0 > ratio * (double)b.d1);
+}
+
+// kernel A of the ordered compaction: the accept flag of every query and the accepted count of every workgroup (pair = blockIdx.z)
+__global__ __launch_bounds__(256) void mutual_flag_kernel(MutualJobs J, const Best2* __restrict__ knn, double ratio,
+                                                          uint8_t* __restrict__ flags, int* __restrict__ wgcount, int nblk)
+{
+    __shared__ int s_n[4];
+    const int p = blockIdx.z, tid = threadIdx.x;
+    const int nq = mutual_count(J.nq[p], J.q_cap);
+    if ((int)blockIdx.x * 256 >= nq) return;
+    const int i = blockIdx.x * 256 + tid;
+    const bool ok = i < nq && mutual_keep(knn, J, p, i, ratio);
+    if (i < nq) flags[(size_t)p * J.q_cap + i] = ok ? 1 : 0;
+    const unsigned long long m = __ballot(ok);
+    if ((tid & 63) == 0) s_n[tid >> 6] = __popcll(m);
+    __syncthreads();
+    if (tid == 0) wgcount[(size_t)p * nblk + blockIdx.x] = s_n[0] + s_n[1] + s_n[2] + s_n[3];
+}
+
+// kernel B: each workgroup sums the counts of the workgroups before it (in LDS; no communication between workgroups of this
+// launch) and writes its accepted rows at their rank, in ascending query order; the last workgroup writes the total
+__global__ __launch_bounds__(256) void mutual_compact_kernel(MutualJobs J, const Best2* __restrict__ knn, const uint8_t* __restrict__ flags,
+                                                             const int* __restrict__ wgcount, int nblk)
+{
+    __shared__ int s_sum[4], s_n[4];
+    const int p = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nq = mutual_count(J.nq[p], J.q_cap);
+    const int used = (nq + 255) >> 8, x = blockIdx.x;
+    if (x >= used && x != 0) return;                       // (workgroup 0 writes the zero total of an empty query set)
+    int s = 0;
+    for (int k = tid; k < x; k += 256) s += wgcount[(size_t)p * nblk + k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    const int i = x * 256 + tid;
+    const bool ok = i < nq && flags[(size_t)p * J.q_cap + i];
+    const unsigned long long m = __ballot(ok);
+    if (lane == 0) { s_sum[wave] = s; s_n[wave] = __popcll(m); }
+    __syncthreads();
+    const int base = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+    int rank = base + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+    for (int w = 0; w < wave; w++) rank += s_n[w];
+    if (ok) {
+        const Best2 a = knn[(size_t)(2 * p) * J.cap + i];
+        int* row = J.out[p] + 3 * (size_t)rank;
+        row[0] = i; row[1] = a.i0; row[2] = a.d0;
+    }
+    if (tid == 0 && x == (used > 0 ? used - 1 : 0)) *J.nout[p] = base + s_n[0] + s_n[1] + s_n[2] + s_n[3];
+}
+
 } // namespace
 
 // int8 matrix-core path: scratch_x holds the expanded (+-1 bytes) queries and trains, efx_knn2_mfma_scratch() bytes
@@ -565,5 +875,65 @@ hipError_t efx_launch_crosscheck(const int* q2t, const int* t2q, int nq, int* ma
 {
     if (nq <= 0) return hipSuccess;
     hipLaunchKernelGGL(crosscheck_kernel, dim3((nq + 255) / 256), dim3(256), 0, stream, q2t, t2q, nq, match);
+    return hipGetLastError();
+}
+
+// ---- mutual matching on device counts (efx_api.cpp: efx_match_mutual_async / efx_match_mutual_batch_async) ----
+// Expands nmat (<= 2 * EFX_MAX_BATCH) descriptor matrices in one launch: matrix i -> dst[i], room for round_up(cap_max, 256) rows of
+// efx_mutual_expanded_row(desc_bytes, fp4) bytes
+size_t efx_mutual_expanded_row(int desc_bytes, int fp4) { return (size_t)desc_bytes * (fp4 ? 4 : 8); }
+
+hipError_t efx_launch_mutual_expand(int nmat, const uint8_t* const* src, const size_t* pitch, const int* const* n, const int* cap,
+                                    int cap_max, int desc_bytes, int fp4, uint8_t* const* dst, hipStream_t stream)
+{
+    const size_t rows_pad = (size_t)((cap_max + 255) & ~255);
+    if (nmat <= 0 || rows_pad == 0) return hipSuccess;
+    if (nmat > 2 * EFX_MAX_BATCH) return hipErrorInvalidValue;
+    ExpandJobs E = {};
+    for (int i = 0; i < nmat; i++) { E.src[i] = src[i]; E.pitch[i] = pitch[i]; E.n[i] = n[i]; E.cap[i] = cap[i]; E.dst[i] = dst[i]; }
+    const size_t g = rows_pad * (size_t)(desc_bytes / 2);
+    const dim3 grid((unsigned)((g + 255) / 256), 1, (unsigned)nmat);
+    if (fp4) hipLaunchKernelGGL(expand_dc_kernel<true>, grid, dim3(256), 0, stream, E, desc_bytes);
+    else hipLaunchKernelGGL(expand_dc_kernel<false>, grid, dim3(256), 0, stream, E, desc_bytes);
+    return hipGetLastError();
+}
+
+// One chain of npairs (<= EFX_MAX_BATCH) pairs: search both directions (one launch), merge (one), flag (one), compact (one).
+// path 0: popcount on the raw rows q / t; 1: int8 matrix cores, 2: FP4 matrix cores, on expanded rows.  Scratch (bytes):
+// partial 2 npairs x nchunks x cap x 16, knn 2 npairs x cap x 16, flags npairs x q_cap, wgcount npairs x ceil(q_cap / 256) x 4,
+// cap = max(q_cap, t_cap)
+hipError_t efx_launch_mutual(int npairs, const uint8_t* const* q, const uint8_t* const* t, const int* const* nq, const int* const* nt,
+                             size_t q_pitch, size_t t_pitch, int q_cap, int t_cap, int desc_bytes, double ratio,
+                             int* const* out, int* const* nout, int path, int nchunks,
+                             void* partial, void* knn, void* flags, void* wgcount, hipStream_t stream)
+{
+    if (npairs <= 0) return hipSuccess;
+    if (npairs > EFX_MAX_BATCH || nchunks < 1) return hipErrorInvalidValue;
+    MutualJobs J = {};
+    for (int p = 0; p < npairs; p++) { J.q[p] = q[p]; J.t[p] = t[p]; J.nq[p] = nq[p]; J.nt[p] = nt[p]; J.out[p] = out[p]; J.nout[p] = nout[p]; }
+    J.q_pitch = q_pitch; J.t_pitch = t_pitch;
+    J.q_cap = q_cap; J.t_cap = t_cap; J.cap = q_cap > t_cap ? q_cap : t_cap;
+    J.nchunks = nchunks;
+    const unsigned xb = (unsigned)((J.cap + 255) / 256 > 0 ? (J.cap + 255) / 256 : 1);
+    const int nblk = (q_cap + 255) / 256 > 0 ? (q_cap + 255) / 256 : 1;
+    Best2* part = static_cast<Best2*>(partial);
+    Best2* best = static_cast<Best2*>(knn);
+    const dim3 grid(xb, (unsigned)nchunks, 2u * (unsigned)npairs);
+    if (path == 0) {
+        if (desc_bytes == 32) hipLaunchKernelGGL(knn2_dc_kernel<8>, grid, dim3(256), 0, stream, J, part);
+        else hipLaunchKernelGGL(knn2_dc_kernel<16>, grid, dim3(256), 0, stream, J, part);
+    } else if (path == 2) {
+        if (desc_bytes == 32) hipLaunchKernelGGL((knn2_mfma_dc_kernel<256, true, true>), grid, dim3(512), 0, stream, J, part);
+        else hipLaunchKernelGGL((knn2_mfma_dc_kernel<512, true, true>), grid, dim3(512), 0, stream, J, part);
+    } else {
+        if (desc_bytes == 32) hipLaunchKernelGGL((knn2_mfma_dc_kernel<256, false, false>), grid, dim3(512), 0, stream, J, part);
+        else hipLaunchKernelGGL((knn2_mfma_dc_kernel<512, false, false>), grid, dim3(512), 0, stream, J, part);
+    }
+    hipLaunchKernelGGL(knn2_merge_dc_kernel, dim3(xb, 1, 2u * (unsigned)npairs), dim3(256), 0, stream, J, (const Best2*)part, best);
+    const dim3 fgrid((unsigned)nblk, 1, (unsigned)npairs);
+    hipLaunchKernelGGL(mutual_flag_kernel, fgrid, dim3(256), 0, stream, J, (const Best2*)best, ratio, static_cast<uint8_t*>(flags),
+                       static_cast<int*>(wgcount), nblk);
+    hipLaunchKernelGGL(mutual_compact_kernel, fgrid, dim3(256), 0, stream, J, (const Best2*)best, (const uint8_t*)flags,
+                       (const int*)wgcount, nblk);
     return hipGetLastError();
 }

@@ -332,6 +332,58 @@ public:
             throw Exception(EFX_ERR_HIP, "download failed");
         for (int i = 0; i < nq; i++) if (hi[i] >= 0) matches.push_back(DMatch{ i, hi[i], hd[i] });
     }
+    // The mutual ratio-test filter of samples/sample_image_sequence.cpp:114-137 on the device: d_nq / d_nt are
+    // device ints (e.g. detectAndComputeBatchAsync's counts; nullptr: every row), read on the device; matches receives
+    // query.rows x 3 ints {queryIdx, trainIdx, distance}, valid below *d_nmatches.  No host synchronisation.
+    void matchMutualAsync(const DeviceMatrix& query, const int* d_nq, const DeviceMatrix& train, const int* d_nt, int descBytes,
+                          DeviceMatrix& matches, int* d_nmatches, double ratio = 0.9, hipStream_t stream = nullptr)
+    {
+        matches.create(query.rows > 0 ? query.rows : 1, 3, 4);
+        check(efx_match_mutual_async(m_, static_cast<const uint8_t*>(query.data()), query.step, d_nq, query.rows,
+                                     static_cast<const uint8_t*>(train.data()), train.step, d_nt, train.rows, descBytes, ratio,
+                                     static_cast<int*>(matches.data()), d_nmatches, stream));
+    }
+    // pairs (query[i], train[i]) in one call (one launch of every kernel per 16 pairs); the matrices of one side have one shape
+    void matchMutualBatchAsync(const std::vector<const DeviceMatrix*>& query, const std::vector<const int*>& d_nq,
+                               const std::vector<const DeviceMatrix*>& train, const std::vector<const int*>& d_nt, int descBytes,
+                               std::vector<DeviceMatrix>& matches, const std::vector<int*>& d_nmatches, double ratio = 0.9,
+                               hipStream_t stream = nullptr)
+    {
+        const size_t n = query.size();
+        if (train.size() != n || d_nq.size() != n || d_nt.size() != n || d_nmatches.size() != n)
+            throw Exception(EFX_ERR_BAD_ARG, "one train matrix, count pair and output per query matrix");
+        if (n == 0) return;
+        matches.resize(n);
+        std::vector<const uint8_t*> q(n), t(n);
+        std::vector<int*> out(n);
+        for (size_t i = 0; i < n; i++) {
+            if (query[i]->rows != query[0]->rows || query[i]->step != query[0]->step || train[i]->rows != train[0]->rows ||
+                train[i]->step != train[0]->step)
+                throw Exception(EFX_ERR_BAD_ARG, "the query (train) matrices of a batch have one shape");
+            matches[i].create(query[0]->rows > 0 ? query[0]->rows : 1, 3, 4);
+            q[i] = static_cast<const uint8_t*>(query[i]->data()); t[i] = static_cast<const uint8_t*>(train[i]->data());
+            out[i] = static_cast<int*>(matches[i].data());
+        }
+        check(efx_match_mutual_batch_async(m_, (int)n, q.data(), query[0]->step, d_nq.data(), query[0]->rows, t.data(), train[0]->step,
+                                           d_nt.data(), train[0]->rows, descBytes, ratio, out.data(), d_nmatches.data(), stream));
+    }
+    // host convenience: nq / nt rows of device descriptors, the kept pairs downloaded (one stream synchronisation)
+    void matchMutual(const DeviceMatrix& query, int nq, const DeviceMatrix& train, int nt, int descBytes, std::vector<DMatch>& matches,
+                     double ratio = 0.9, hipStream_t stream = nullptr)
+    {
+        matches.clear();
+        idx_.create(1, 3 * (nq > 0 ? nq : 1) + 1, 4);
+        int* d = static_cast<int*>(idx_.data());
+        check(efx_match_mutual_async(m_, static_cast<const uint8_t*>(query.data()), query.step, nullptr, nq,
+                                     static_cast<const uint8_t*>(train.data()), train.step, nullptr, nt, descBytes, ratio,
+                                     d + 1, d, stream));
+        int k = 0;
+        if (hipStreamSynchronize(stream) != hipSuccess || hipMemcpy(&k, d, 4, hipMemcpyDeviceToHost) != hipSuccess)
+            throw Exception(EFX_ERR_HIP, "download failed");
+        std::vector<int> h((size_t)3 * k);
+        if (k > 0 && hipMemcpy(h.data(), d + 1, h.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) throw Exception(EFX_ERR_HIP, "download failed");
+        for (int i = 0; i < k; i++) matches.push_back(DMatch{ h[3 * i], h[3 * i + 1], h[3 * i + 2] });
+    }
 private:
     void check(int rc) const { if (rc != EFX_OK) throw Exception(rc, efx_matcher_last_error(m_)); }
     efx_matcher* m_ = nullptr;

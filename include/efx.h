@@ -247,6 +247,32 @@ int efx_match_crosscheck_async(efx_matcher* m, const uint8_t* d_query, size_t q_
                                const uint8_t* d_train, size_t t_pitch, int nt, int desc_bytes,
                                int* d_match, int* d_dist, void* stream);
 
+/* The filter of samples/sample_image_sequence.cpp:114-137 on the device: knnMatch(k = 2) in both directions, and
+ * pair (i, j = m12[0].train) is kept iff  !((double)m12.d0 > ratio * (double)m12.d1),  !((double)m21.d0 > ratio * (double)m21.d1)
+ * (m21 = the best two queries of train j) and  m21[0].train == i.  Ties go to the lower index in both directions (as knn2); a
+ * missing second neighbour passes its ratio test; ratio >= 1 gives the cross-checked pairs.  Row counts are read on the DEVICE:
+ * d_nq / d_nt point to an int written earlier on the stream (e.g. a detect call's d_count), clamped to [0, capacity]; NULL means
+ * "count = capacity".  Rows at or beyond the count are never read.  Grids and scratch are sized from the capacities.
+ * Output: d_matches[k] = {queryIdx, trainIdx, distance} (3 x int32), k < *d_nmatches, in ascending queryIdx; room for q_capacity
+ * rows.  No host synchronisation inside (the matcher's scratch grows with a device-wide wait the first time larger capacities
+ * arrive). */
+int efx_match_mutual_async(efx_matcher* m,
+                           const uint8_t* d_query, size_t q_pitch, const int* d_nq, int q_capacity,
+                           const uint8_t* d_train, size_t t_pitch, const int* d_nt, int t_capacity,
+                           int desc_bytes, double ratio, int* d_matches, int* d_nmatches, void* stream);
+
+/* npairs independent (query, train) pairs: one launch of every kernel of the path per chain of up to EFX_MAX_BATCH = 16 pairs
+ * (pair = blockIdx.z), more pairs in several chains; every pair's output equals efx_match_mutual_async's on it, bit for bit.  A
+ * descriptor matrix that appears in several pairs of a chain (same rows, pitch, count pointer and capacity: frame i is the train of
+ * pair i - 1 and the query of pair i) is expanded once, and one the previous chain left expanded is not expanded again.  Scratch is
+ * bounded by one chain, not by npairs: at most 32 expanded matrices of max(q_capacity, t_capacity) rows rounded up to 256, 128 bytes
+ * (256 bit) or 256 bytes (512 bit) per row with the FP4 matrix cores, twice that with EFX_MATCH_NO_FP4.  d_nq / d_nt may be NULL
+ * (every count = its capacity). */
+int efx_match_mutual_batch_async(efx_matcher* m, int npairs,
+                                 const uint8_t* const* d_query, size_t q_pitch, const int* const* d_nq, int q_capacity,
+                                 const uint8_t* const* d_train, size_t t_pitch, const int* const* d_nt, int t_capacity,
+                                 int desc_bytes, double ratio, int* const* d_matches, int* const* d_nmatches, void* stream);
+
 /* Batched variant (SURVEY 8b "batched variants (..., nframes) for roofline-sized launches"; the loop of
  * samples/sample_image_sequence.cpp:70-105): nframes independent frames of one size in one call.  Frame i belongs to context
  * ctxs[i % nctx] and stream streams[i % nctx]; the frames of ONE context go through ONE launch of every kernel of the path (frame =
