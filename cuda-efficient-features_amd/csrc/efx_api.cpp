@@ -405,14 +405,10 @@ struct efx_describer { Describer d; };
 struct efx_matcher {
     bool no_mfma = getenv("EFX_MATCH_NO_MFMA") != nullptr;        // variant knob (tests: force the popcount kernel), read when the matcher is created
     bool no_fp4 = getenv("EFX_MATCH_NO_FP4") != nullptr;          // ... the int8 matrix-core kernel instead of the FP4 one
-    DevBuf scratch, expanded, a_idx, a_dist, b_idx, b_dist;
-    DevBuf mx, mpart, mknn, mflag;  // mutual matching: expanded matrices, per-chunk best two, best-two lists, flags + workgroup counts
+    // expanded matrices (matrix cores), per-chunk best two, knnMatch lists (crossCheck, mutual), mutual flags + workgroup counts
+    DevBuf x, part, knn, flag;
     std::string err;
-    ~efx_matcher()
-    {
-        scratch.release(); expanded.release(); a_idx.release(); a_dist.release(); b_idx.release(); b_dist.release();
-        mx.release(); mpart.release(); mknn.release(); mflag.release();
-    }
+    ~efx_matcher() { x.release(); part.release(); knn.release(); flag.release(); }
 };
 
 struct efx_context {
@@ -2021,35 +2017,49 @@ static int match_args_ok(efx_matcher* m, const uint8_t* q, size_t qp, int nq, co
     return EFX_OK;
 }
 
+// The search kernel of a call: 0 popcount, 1 int8 matrix cores (EFX_MATCH_NO_FP4), 2 FP4 (MX) matrix cores -- the distance
+// matrix as a GEMM (match_kernels.hip).  The matrix cores take at least 128 queries and min_nt trains: knnMatch 64, mutual
+// matching 128 (on capacities, for both directions).
+static int match_path(const efx_matcher* m, int nq, int nt, int min_nt)
+{
+    if (m->no_mfma || nq < 128 || nt < min_nt) return 0;
+    return m->no_fp4 ? 1 : 2;
+}
+
+// Train chunks per job (grid.y) of a launch of njobs jobs of up to nq queries and nt trains.  Popcount: enough (query block,
+// chunk) workgroups to fill the chip, ~4 per CU.  Matrix cores: the workgroups of all jobs run in ceil(workgroups / resident)
+// rounds, each over ceil(tiles / chunks) tiles plus a fixed cost of about two (query fragments, partial rows); the count with
+// the least rounds x work wins, but no job gets more workgroups than one round holds -- fewer chunks mean fewer best-two updates
+// per wave (a wave's updates fall off as 1 / trains seen).  One job: the most chunks that fit one round (two 512-thread
+// workgroups per CU for 512 bits, three for 256); 40 000 x 40 000: 512 bit 2 / 3 / 4 / 6 chunks 0.576 / 0.436 / 0.436 /
+// 0.469 ms, 256 bit 0.376 / 0.295 / 0.277 / 0.323.
+static int match_chunks(int path, int db, int njobs, int nq, int nt)
+{
+    const int qblocks = std::max(1, (nq + 255) / 256);
+    if (path == 0) return std::max(1, std::min({ 64, std::max(nt, 1), 1024 / (njobs * qblocks) }));
+    const int resident = efx_knn2_mfma_resident_workgroups(db, path == 2 ? 1 : 0);
+    const int ntiles = std::max(1, (nt + 31) / 32);
+    const int most = std::min({ 64, ntiles, std::max(1, resident / qblocks) });
+    int best = 1;
+    long best_cost = -1;
+    for (int c = 1; c <= most; c++) {
+        const long rounds = ((long)njobs * qblocks * c + resident - 1) / resident;
+        const long cost = rounds * ((ntiles + c - 1) / c + 2);
+        if (best_cost < 0 || cost <= best_cost) { best = c; best_cost = cost; }
+    }
+    return best;
+}
+
 static int knn2_run(efx_matcher* m, const uint8_t* q, size_t qp, int nq, const uint8_t* t, size_t tp, int nt, int db,
                     int* idx, int* dist, hipStream_t stream)
 {
     if (nq == 0) return EFX_OK;
-    if (nq >= 128 && nt >= 64 && !m->no_mfma) {
-        // large sets: the distance matrix as a GEMM on the matrix cores (match_kernels.hip): FP4 (MX) operands, int8 with EFX_MATCH_NO_FP4
-        // (query block, train chunk) pairs: ONE round of the workgroups the chip holds of the kernel that will run (two 512-thread
-        // workgroups per CU for 512 bits, three for 256) -- fewer chunks mean fewer best-two updates per wave (a wave's updates
-        // fall off as 1 / trains seen), a second, partly filled round costs as much as the first; 40 000 x 40 000: 512 bit
-        // 2 / 3 / 4 / 6 chunks 0.576 / 0.436 / 0.436 / 0.469 ms, 256 bit 0.376 / 0.295 / 0.277 / 0.323
-        int nchunks = efx_knn2_mfma_resident_workgroups(db, m->no_fp4 ? 0 : 1) / ((nq + 255) / 256);
-        { static const int env = [] { const char* v = getenv("EFX_MATCH_CHUNKS"); return v ? atoi(v) : 0; }(); if (env > 0) nchunks = env; }   // INVESTIGATION knob
-        if (nchunks < 1) nchunks = 1;
-        if (nchunks > 64) nchunks = 64;
-        const int ntiles = (nt + 31) / 32;
-        if (nchunks > ntiles) nchunks = ntiles;
-        HIP_TRY(m->err, m->scratch.reserve((size_t)nchunks * nq * 16));
-        HIP_TRY(m->err, m->expanded.reserve(efx_knn2_mfma_scratch(nq, nt, db)));
-        hipError_t e = efx_launch_knn2_mfma(q, qp, nq, t, tp, nt, db, m->expanded.p, m->scratch.p, nchunks, idx, dist, stream, m->no_fp4 ? 0 : 1);
-        if (e != hipSuccess) return set_err(m->err, EFX_ERR_HIP, "knn launch failed: %s", hipGetErrorString(e));
-        return EFX_OK;
-    }
-    // enough (query block, train chunk) pairs to fill the chip: ~4 workgroups per CU
-    int nchunks = 1024 / ((nq + 255) / 256);
-    if (nchunks < 1) nchunks = 1;
-    if (nchunks > 64) nchunks = 64;
-    if (nchunks > nt) nchunks = nt > 0 ? nt : 1;
-    HIP_TRY(m->err, m->scratch.reserve((size_t)nchunks * nq * 16));
-    hipError_t e = efx_launch_knn2(q, qp, nq, t, tp, nt, db, m->scratch.p, nchunks, idx, dist, stream);
+    const int path = match_path(m, nq, nt, 64);
+    const int nchunks = match_chunks(path, db, 1, nq, nt);
+    HIP_TRY(m->err, m->part.reserve((size_t)nchunks * nq * 16));
+    if (path) HIP_TRY(m->err, m->x.reserve(efx_knn2_mfma_scratch(nq, nt, db)));
+    const hipError_t e = path ? efx_launch_knn2_mfma(q, qp, nq, t, tp, nt, db, m->x.p, m->part.p, nchunks, idx, dist, stream, path == 2)
+                              : efx_launch_knn2(q, qp, nq, t, tp, nt, db, m->part.p, nchunks, idx, dist, stream);
     if (e != hipSuccess) return set_err(m->err, EFX_ERR_HIP, "knn launch failed: %s", hipGetErrorString(e));
     return EFX_OK;
 }
@@ -2072,39 +2082,25 @@ int efx_match_crosscheck_async(efx_matcher* m, const uint8_t* d_query, size_t q_
     if (rc) return rc;
     if (nq == 0) return EFX_OK;
     if (!d_match) return set_err(m->err, EFX_ERR_BAD_ARG, "null outputs");
-    HIP_TRY(m->err, m->a_idx.reserve((size_t)nq * 8)); HIP_TRY(m->err, m->a_dist.reserve((size_t)nq * 8));
-    HIP_TRY(m->err, m->b_idx.reserve((size_t)(nt > 0 ? nt : 1) * 8)); HIP_TRY(m->err, m->b_dist.reserve((size_t)(nt > 0 ? nt : 1) * 8));
-    rc = knn2_run(m, d_query, q_pitch, nq, d_train, t_pitch, nt, desc_bytes, (int*)m->a_idx.p, (int*)m->a_dist.p, (hipStream_t)stream);
+    const size_t na = 2 * (size_t)nq, nb = 2 * (size_t)std::max(nt, 1);      // ints of a list: query -> train, train -> query
+    HIP_TRY(m->err, m->knn.reserve((na + nb) * 8));
+    int* a_idx = static_cast<int*>(m->knn.p);
+    int* a_dist = a_idx + na;
+    int* b_idx = a_dist + na;
+    rc = knn2_run(m, d_query, q_pitch, nq, d_train, t_pitch, nt, desc_bytes, a_idx, a_dist, (hipStream_t)stream);
     if (rc) return rc;
-    rc = knn2_run(m, d_train, t_pitch, nt, d_query, q_pitch, nq, desc_bytes, (int*)m->b_idx.p, (int*)m->b_dist.p, (hipStream_t)stream);
+    rc = knn2_run(m, d_train, t_pitch, nt, d_query, q_pitch, nq, desc_bytes, b_idx, b_idx + nb, (hipStream_t)stream);
     if (rc) return rc;
-    hipError_t e = efx_launch_crosscheck((const int*)m->a_idx.p, (const int*)m->b_idx.p, nq, d_match, (hipStream_t)stream);
+    hipError_t e = efx_launch_crosscheck(a_idx, b_idx, nq, d_match, (hipStream_t)stream);
     if (e != hipSuccess) return set_err(m->err, EFX_ERR_HIP, "crosscheck launch failed: %s", hipGetErrorString(e));
     if (d_dist) {
         // distance of the kept pairs = first column of the query->train result
-        HIP_TRY(m->err, hipMemcpy2DAsync(d_dist, 4, m->a_dist.p, 8, 4, (size_t)nq, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        HIP_TRY(m->err, hipMemcpy2DAsync(d_dist, 4, a_dist, 8, 4, (size_t)nq, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     }
     return EFX_OK;
 }
 
 // ---- mutual ratio-test matching on device counts ----
-// Train chunks per job of the matrix-core search: the (query block, chunk) workgroups of all jobs of a launch run in
-// ceil(workgroups / resident) rounds, each workgroup over ceil(tiles / chunks) tiles plus a fixed cost of about two tiles
-// (query fragments, partial rows); the count with the least rounds x work wins, fewer chunks on ties.  For ONE job this picks
-// knn2_run's single round (40 000 x 40 000: three chunks).
-static int mutual_mfma_chunks(int resident, int njobs, int cap)
-{
-    const long qblocks = (long)njobs * ((cap + 255) / 256);
-    const int ntiles = (cap + 31) / 32;
-    int best = 1; long best_cost = -1;
-    for (int c = 1; c <= 64 && c <= (ntiles > 0 ? ntiles : 1); c++) {
-        const long rounds = (qblocks * c + resident - 1) / resident;
-        const long cost = rounds * ((ntiles + c - 1) / c + 2);
-        if (best_cost < 0 || cost < best_cost) { best = c; best_cost = cost; }
-    }
-    return best;
-}
-
 int efx_match_mutual_batch_async(efx_matcher* m, int npairs,
                                  const uint8_t* const* d_query, size_t q_pitch, const int* const* d_nq, int q_capacity,
                                  const uint8_t* const* d_train, size_t t_pitch, const int* const* d_nt, int t_capacity,
@@ -2125,14 +2121,11 @@ int efx_match_mutual_batch_async(efx_matcher* m, int npairs,
         if (!d_matches[p] || !d_nmatches[p]) return set_err(m->err, EFX_ERR_BAD_ARG, "null outputs");
     }
     const hipStream_t st = (hipStream_t)stream;
-    // matrix cores when both directions qualify (knn2_run's rule, on capacities); the popcount kernel otherwise
-    const int path = (!m->no_mfma && q_capacity >= 128 && t_capacity >= 128) ? (m->no_fp4 ? 1 : 2) : 0;
+    const int path = match_path(m, q_capacity, t_capacity, 128);
     const int cap = std::max(q_capacity, t_capacity);
     const int chain = std::min(npairs, EFX_MAX_BATCH);     // pairs of the largest launch chain
     const int njobs = 2 * chain;
-    int nchunks;
-    if (path) nchunks = mutual_mfma_chunks(efx_knn2_mfma_resident_workgroups(db, path == 2 ? 1 : 0), njobs, cap);
-    else nchunks = std::max(1, std::min(std::min(64, std::max(cap, 1)), 1024 / (njobs * std::max(1, (cap + 255) / 256))));
+    const int nchunks = match_chunks(path, db, njobs, cap, cap);
 
     // Expanded matrices live in slots planned per chain: a chain's distinct matrices (rows, pitch, count pointer, capacity) take
     // one slot each and are expanded once, then serve as the query operand of one direction and the train operand of the other in
@@ -2178,11 +2171,11 @@ int efx_match_mutual_batch_async(efx_matcher* m, int npairs,
     const size_t flag_bytes = align_up((size_t)chain * (size_t)std::max(q_capacity, 1), 256);
     // every block is reserved before the first launch: a regrow (the only place this path may wait on the host) never finds
     // work of THIS call in flight
-    HIP_TRY(m->err, m->mx.reserve(std::max<size_t>(slot.size() * xrow, 1)));
-    HIP_TRY(m->err, m->mpart.reserve((size_t)njobs * nchunks * std::max(cap, 1) * 16));
-    HIP_TRY(m->err, m->mknn.reserve((size_t)njobs * std::max(cap, 1) * 16));
-    HIP_TRY(m->err, m->mflag.reserve(flag_bytes + (size_t)chain * nblk * 4));
-    uint8_t* const xbase = static_cast<uint8_t*>(m->mx.p);
+    HIP_TRY(m->err, m->x.reserve(std::max<size_t>(slot.size() * xrow, 1)));
+    HIP_TRY(m->err, m->part.reserve((size_t)njobs * nchunks * std::max(cap, 1) * 16));
+    HIP_TRY(m->err, m->knn.reserve((size_t)njobs * std::max(cap, 1) * 16));
+    HIP_TRY(m->err, m->flag.reserve(flag_bytes + (size_t)chain * nblk * 4));
+    uint8_t* const xbase = static_cast<uint8_t*>(m->x.p);
     const int fp4 = path == 2 ? 1 : 0;
     for (int c = 0, p0 = 0; p0 < npairs; c++, p0 += EFX_MAX_BATCH) {
         const int k = std::min(npairs - p0, EFX_MAX_BATCH);
@@ -2206,8 +2199,8 @@ int efx_match_mutual_batch_async(efx_matcher* m, int npairs,
         }
         const size_t xp = efx_mutual_expanded_row(db, fp4);
         hipError_t e = efx_launch_mutual(k, q, t, nq, nt, path ? xp : q_pitch, path ? xp : t_pitch, q_capacity, t_capacity, db, ratio,
-                                         d_matches + p0, d_nmatches + p0, path, nchunks, m->mpart.p, m->mknn.p, m->mflag.p,
-                                         static_cast<uint8_t*>(m->mflag.p) + flag_bytes, st);
+                                         d_matches + p0, d_nmatches + p0, path, nchunks, m->part.p, m->knn.p, m->flag.p,
+                                         static_cast<uint8_t*>(m->flag.p) + flag_bytes, st);
         if (e != hipSuccess) return set_err(m->err, EFX_ERR_HIP, "mutual match launch failed: %s", hipGetErrorString(e));
     }
     return EFX_OK;

@@ -269,7 +269,7 @@ def test_natural_statistics_4k(cef, threaded_oracle, kind):
 def test_matcher_40k_by_40k_all_three_kernels(cef, monkeypatch, nbytes, kind):
     """The quoted matcher workload at its FULL size: knnMatch(k = 2) of 40 000 x 40 000 descriptors of 256 and
     512 bit through the FP4 (MX) matrix-core kernel, the int8 matrix-core kernel and the popcount kernel -- at this size the
-    matrix-core kernels cut the train set into occupancy-sized chunks and merge the per-chunk best-twos (knn2_merge_kernel), a
+    matrix-core kernels cut the train set into occupancy-sized chunks and merge the per-chunk best-twos (knn2_merge_dc_kernel), a
     chunk count no smaller case reaches -- against oracle/matcher_oracle.c (OpenMP popcounts; sample_image_sequence.cpp:114-144).
     `ties`: descriptors drawn from a pool of 300 with noisy copies, so that most queries have several trains at their best and
     second-best distance and the lower train index must win across chunk boundaries."""

@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage (GPU box, repo root): tools/microbench/match_ab.sh "<EXTRA flags of variant B>" (e.g. -DEFX_MATCH_NO_PRELOAD=1)  -- the matcher with and without a build flag, alternating, then full-size parity of B
+# usage (GPU box, repo root): tools/microbench/match_ab.sh "<EXTRA flags of variant B>" (e.g. -O2)  -- the matcher with and without a build flag, alternating, then full-size parity of B
 cd "$GRAFT_REPO_ROOT"
 build() { rm -f cuda-efficient-features_amd/csrc/match_kernels.o; make -s -C cuda-efficient-features_amd/csrc EXTRA="$1" 2>&1 | grep -E "error" | head -3; }
 for rep in 1 2; do
