@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "efx_describer_compute", "efx_describer_hashsift_debug_async",
     "efx_matcher_create", "efx_matcher_destroy", "efx_matcher_last_error", "efx_match_knn2_async",
     "efx_match_crosscheck_async", "efx_match_mutual_async", "efx_match_mutual_batch_async",
+    "efx_default_ransac_params", "efx_match_homography_async", "efx_match_homography_batch_async",
     "efx_detect_and_compute_batch_async", "efx_detect_and_compute_masked_async", "efx_compute_provided_async", "efx_detect_and_compute_ex",
     "efx_ic_angles_async", "efx_ic_angles", "efx_descriptors_to_csv",
     "efx_cvt_gray_async", "efx_host_alloc", "efx_host_free", "efx_uploader_create", "efx_uploader_destroy",
@@ -61,6 +62,14 @@ class EfxError(RuntimeError):
 class Params(C.Structure):
     _fields_ = [("nfeatures", C.c_int), ("scale_factor", C.c_float), ("nlevels", C.c_int), ("first_level", C.c_int),
                 ("fast_threshold", C.c_int), ("nonmax_radius", C.c_int), ("descriptor_type", C.c_int)]
+
+
+class RansacParams(C.Structure):
+    """efx_ransac_params (include/efx.h)"""
+    _fields_ = [("hypotheses", C.c_int), ("threshold", C.c_float), ("seed", C.c_ulonglong), ("refine", C.c_int)]
+
+
+HOMOGRAPHY_BYTES = 88          # sizeof(efx_homography): double H[9]; int ninliers, hypothesis, valid_hypotheses, refined
 
 
 class LevelStats(C.Structure):
@@ -146,6 +155,14 @@ def lib():
         L.efx_match_mutual_batch_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
                                                    C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                                    C.c_void_p]
+        L.efx_default_ransac_params.restype = None
+        L.efx_default_ransac_params.argtypes = [C.POINTER(RansacParams)]
+        L.efx_match_homography_async.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RansacParams), C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]
+        L.efx_match_homography_batch_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
+                                                       C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RansacParams), C.c_void_p,
+                                                       C.c_void_p, C.c_void_p]
         L.efx_detect_and_compute_batch_async.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t,
                                                          C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         L.efx_detect_and_compute_masked_async.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t,
@@ -796,6 +813,60 @@ class BFMatcher:
         b.run()
         return b.matches, b.nmatches
 
+    @staticmethod
+    def _kps(t):
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == 5
+                and t.stride(1) == 1):
+            raise EfxError(-1, "keypoints must be a 5 x capacity float32 CUDA tensor")
+        return t
+
+    @staticmethod
+    def _matches(t):
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 2 and t.shape[1] == 3
+                and (t.shape[0] == 0 or (t.stride(0) == 3 and t.stride(1) == 1))):
+            raise EfxError(-1, "matches must be a capacity x 3 int32 CUDA tensor with tight rows")
+        return t
+
+    @staticmethod
+    def _ransac(threshold, hypotheses, seed, refine):
+        p = RansacParams()
+        p.hypotheses, p.threshold, p.seed, p.refine = int(hypotheses), float(threshold), int(seed) & (2 ** 64 - 1), 1 if refine else 0
+        return p
+
+    @staticmethod
+    def _homography_outputs(capacity, device):
+        """(raw result buffer, H 3 x 3 float64 view, info int32[4] view, mask uint8[capacity])"""
+        import torch
+        buf = torch.empty((HOMOGRAPHY_BYTES,), dtype=torch.uint8, device=device)
+        H = buf[:72].view(torch.float64).view(3, 3)
+        info = buf[72:].view(torch.int32)
+        mask = torch.empty((max(capacity, 1),), dtype=torch.uint8, device=device)[:capacity]
+        return buf, H, info, mask
+
+    def findHomography(self, kps_q, kps_t, matches, nmatches=None, threshold=3.0, hypotheses=2048, seed=0, refine=True, stream=None):
+        """cv::findHomography(src, dst, RANSAC) on matched keypoints, on the device (DESIGN.md S16): src = LOCATION[queryIdx] of kps_q,
+        dst = LOCATION[trainIdx] of kps_t (5 x capacity float32 keypoint matrices), matches = capacity x 3 int32 rows
+        {queryIdx, trainIdx, distance} (matchMutual's output), nmatches = their count (1-element int32 CUDA tensor read on the
+        device; None: every row).  Returns device tensors (H 3 x 3 float64, info int32[4] = {ninliers, hypothesis (-1: no model),
+        valid_hypotheses, refined}, mask uint8[capacity]); H and info are views of one result buffer.  No host sync."""
+        q, t, m = self._kps(kps_q), self._kps(kps_t), self._matches(matches)
+        c = self._count(nmatches)
+        p = self._ransac(threshold, hypotheses, seed, refine)
+        buf, H, info, mask = self._homography_outputs(m.shape[0], m.device)
+        self._check(lib().efx_match_homography_async(self._h, q.data_ptr(), q.stride(0) * 4, q.shape[1], t.data_ptr(), t.stride(0) * 4,
+                                                     t.shape[1], m.data_ptr(), c.data_ptr() if c is not None else None, m.shape[0],
+                                                     C.byref(p), buf.data_ptr(), mask.data_ptr(), _stream_ptr(stream)))
+        return H, info, mask
+
+    def findHomographyBatch(self, kps_qs, kps_ts, matches, nmatches=None, threshold=3.0, hypotheses=2048, seed=0, refine=True,
+                            stream=None):
+        """findHomography over npairs pairs in one call (HomographyBatch, run once): lists (H, info, mask)."""
+        b = HomographyBatch(self, kps_qs, kps_ts, matches, nmatches, threshold, hypotheses, seed, refine, stream)
+        b.run()
+        return b.H, b.info, b.mask
+
 
 class MutualBatch:
     """efx_match_mutual_batch_async with prepared pointer tables (like Batch): pair i matches queries[i] against trains[i], with
@@ -838,6 +909,55 @@ class MutualBatch:
         n, qp, qcap, tp, tcap, db, ratio = self._args
         matcher._check(lib().efx_match_mutual_batch_async(matcher._h, n, self._q, qp, self._nq, qcap, self._t, tp, self._nt, tcap,
                                                           db, ratio, self._m, self._n, _stream_ptr(stream)))
+
+
+class HomographyBatch:
+    """efx_match_homography_batch_async with prepared pointer tables (like MutualBatch): pair i fits a homography to matches[i]
+    (count nmatches[i], optional) between the keypoint matrices kps_qs[i] and kps_ts[i]; every query keypoint matrix has one
+    capacity and pitch, every train matrix too, every match list one capacity.  The outputs are allocated here (H[i] 3 x 3 float64,
+    info[i] int32[4], mask[i] uint8[capacity]); run() crosses the ABI once and may be repeated."""
+
+    def __init__(self, matcher, kps_qs, kps_ts, matches, nmatches=None, threshold=3.0, hypotheses=2048, seed=0, refine=True,
+                 stream=None):
+        n = len(kps_qs)
+        if len(kps_ts) != n or len(matches) != n or (nmatches is not None and len(nmatches) != n):
+            raise EfxError(-1, "one train keypoint matrix, match list (and count) per query keypoint matrix")
+        qs = [BFMatcher._kps(a) for a in kps_qs]
+        ts = [BFMatcher._kps(a) for a in kps_ts]
+        ms = [BFMatcher._matches(a) for a in matches]
+        for group in (qs, ts):
+            for a in group:
+                if a.shape[1] != group[0].shape[1] or a.stride(0) != group[0].stride(0):
+                    raise EfxError(-1, "the query (train) keypoint matrices of a batch have one capacity and pitch")
+        for a in ms:
+            if a.shape[0] != ms[0].shape[0]:
+                raise EfxError(-1, "the match lists of a batch have one capacity")
+        cs = [BFMatcher._count(c) for c in nmatches] if nmatches is not None else None
+        cap = ms[0].shape[0] if n else 0
+        dev = ms[0].device if n else None
+        outs = [BFMatcher._homography_outputs(cap, dev) for _ in range(n)]
+        self._buf = [o[0] for o in outs]
+        self.H = [o[1] for o in outs]
+        self.info = [o[2] for o in outs]
+        self.mask = [o[3] for o in outs]
+        self._params = BFMatcher._ransac(threshold, hypotheses, seed, refine)
+        self._keep = (matcher, qs, ts, ms, cs, stream)
+        P = C.c_void_p
+        k = max(n, 1)
+        self._q = (P * k)(*[P(a.data_ptr()) for a in qs])
+        self._t = (P * k)(*[P(a.data_ptr()) for a in ts])
+        self._m = (P * k)(*[P(a.data_ptr()) for a in ms])
+        self._n = (P * k)(*[P(c.data_ptr()) if c is not None else P() for c in cs]) if cs is not None else None
+        self._r = (P * k)(*[P(a.data_ptr()) for a in self._buf])
+        self._k = (P * k)(*[P(a.data_ptr()) for a in self.mask])
+        self._args = (n, qs[0].stride(0) * 4 if n else 0, qs[0].shape[1] if n else 0, ts[0].stride(0) * 4 if n else 0,
+                      ts[0].shape[1] if n else 0, cap)
+
+    def run(self):
+        matcher, stream = self._keep[0], self._keep[5]
+        n, qp, qcap, tp, tcap, cap = self._args
+        matcher._check(lib().efx_match_homography_batch_async(matcher._h, n, self._q, qp, qcap, self._t, tp, tcap, self._m, self._n,
+                                                              cap, C.byref(self._params), self._r, self._k, _stream_ptr(stream)))
 
 
 def unpack_keypoints(kps):

@@ -384,7 +384,67 @@ public:
         if (k > 0 && hipMemcpy(h.data(), d + 1, h.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) throw Exception(EFX_ERR_HIP, "download failed");
         for (int i = 0; i < k; i++) matches.push_back(DMatch{ h[3 * i], h[3 * i + 1], h[3 * i + 2] });
     }
+    // cv::findHomography(src, dst, RANSAC) on matched keypoints, on the device: kpsQ / kpsT are 5 x capacity keypoint
+    // matrices (row 0 is read), matches the {queryIdx, trainIdx, distance} rows of matchMutualAsync with the count d_nmatches (a
+    // device int, nullptr: every row).  d_result (device) receives the model, mask matches.rows bytes.  No host synchronisation.
+    void findHomographyAsync(const DeviceMatrix& kpsQ, const DeviceMatrix& kpsT, const DeviceMatrix& matches, const int* d_nmatches,
+                             efx_homography* d_result, DeviceMatrix& mask, const efx_ransac_params* params = nullptr,
+                             hipStream_t stream = nullptr)
+    {
+        const efx_ransac_params p = params_or_default(params);
+        mask.create(1, matches.rows > 0 ? matches.rows : 1, 1);
+        check(efx_match_homography_async(m_, kpsQ.data(), kpsQ.step, kpsQ.cols, kpsT.data(), kpsT.step, kpsT.cols,
+                                         static_cast<const int*>(matches.data()), d_nmatches, matches.rows, &p, d_result,
+                                         static_cast<uint8_t*>(mask.data()), stream));
+    }
+    // pairs i in one call (seven launches per 16 pairs): every keypoint matrix of one side has one shape, every match list one capacity
+    void findHomographyBatchAsync(const std::vector<const DeviceMatrix*>& kpsQ, const std::vector<const DeviceMatrix*>& kpsT,
+                                  const std::vector<const DeviceMatrix*>& matches, const std::vector<const int*>& d_nmatches,
+                                  const std::vector<efx_homography*>& d_result, std::vector<DeviceMatrix>& masks,
+                                  const efx_ransac_params* params = nullptr, hipStream_t stream = nullptr)
+    {
+        const size_t n = kpsQ.size();
+        if (kpsT.size() != n || matches.size() != n || d_nmatches.size() != n || d_result.size() != n)
+            throw Exception(EFX_ERR_BAD_ARG, "one train matrix, match list, count and result per query matrix");
+        if (n == 0) return;
+        const efx_ransac_params p = params_or_default(params);
+        masks.resize(n);
+        std::vector<const void*> q(n), t(n);
+        std::vector<const int*> mt(n);
+        std::vector<uint8_t*> mk(n);
+        for (size_t i = 0; i < n; i++) {
+            if (kpsQ[i]->cols != kpsQ[0]->cols || kpsQ[i]->step != kpsQ[0]->step || kpsT[i]->cols != kpsT[0]->cols ||
+                kpsT[i]->step != kpsT[0]->step || matches[i]->rows != matches[0]->rows)
+                throw Exception(EFX_ERR_BAD_ARG, "the keypoint matrices of a side and the match lists of a batch have one shape");
+            masks[i].create(1, matches[0]->rows > 0 ? matches[0]->rows : 1, 1);
+            q[i] = kpsQ[i]->data(); t[i] = kpsT[i]->data(); mt[i] = static_cast<const int*>(matches[i]->data());
+            mk[i] = static_cast<uint8_t*>(masks[i].data());
+        }
+        check(efx_match_homography_batch_async(m_, (int)n, q.data(), kpsQ[0]->step, kpsQ[0]->cols, t.data(), kpsT[0]->step, kpsT[0]->cols,
+                                               mt.data(), d_nmatches.data(), matches[0]->rows, &p, d_result.data(), mk.data(), stream));
+    }
+    // host convenience: the model and the inlier mask downloaded (one stream synchronisation)
+    efx_homography findHomography(const DeviceMatrix& kpsQ, const DeviceMatrix& kpsT, const DeviceMatrix& matches, const int* d_nmatches,
+                                  std::vector<uint8_t>& mask, const efx_ransac_params* params = nullptr, hipStream_t stream = nullptr)
+    {
+        hres_.create(1, (int)sizeof(efx_homography), 1);
+        efx_homography* d = static_cast<efx_homography*>(hres_.data());
+        findHomographyAsync(kpsQ, kpsT, matches, d_nmatches, d, hmask_, params, stream);
+        efx_homography r;
+        mask.resize((size_t)matches.rows);
+        if (hipStreamSynchronize(stream) != hipSuccess || hipMemcpy(&r, d, sizeof(r), hipMemcpyDeviceToHost) != hipSuccess ||
+            (!mask.empty() && hipMemcpy(mask.data(), hmask_.data(), mask.size(), hipMemcpyDeviceToHost) != hipSuccess))
+            throw Exception(EFX_ERR_HIP, "download failed");
+        return r;
+    }
 private:
+    static efx_ransac_params params_or_default(const efx_ransac_params* params)
+    {
+        efx_ransac_params p;
+        efx_default_ransac_params(&p);
+        return params ? *params : p;
+    }
+    DeviceMatrix hres_, hmask_;
     void check(int rc) const { if (rc != EFX_OK) throw Exception(rc, efx_matcher_last_error(m_)); }
     efx_matcher* m_ = nullptr;
     bool cross_;

@@ -273,6 +273,43 @@ int efx_match_mutual_batch_async(efx_matcher* m, int npairs,
                                  const uint8_t* const* d_train, size_t t_pitch, const int* const* d_nt, int t_capacity,
                                  int desc_bytes, double ratio, int* const* d_matches, int* const* d_nmatches, void* stream);
 
+/* RANSAC homography verification of matches (cv::findHomography(src, dst, RANSAC) on the pairs a mutual match keeps), on the
+ * device, one model per pair, DESIGN.md spec S16.  The model maps query to train keypoints: dst ~ H src with src =
+ * LOCATION[queryIdx] of the query keypoint matrix and dst = LOCATION[trainIdx] of the train matrix (the 5xN matrices of a detect
+ * call; only row 0 is read).  d_matches holds {queryIdx, trainIdx, distance} rows (efx_match_mutual_async's output), capacity of
+ * them; the count *d_nmatches is read on the device and clamped to [0, capacity] (NULL: capacity).  A row whose index lies
+ * outside its keypoint matrix's capacity is never an inlier, and a sample that draws it is invalid.  A fixed budget of
+ * `hypotheses` counter-based samples (splitmix64 of seed + 4 h + j, independent of the pair), the most inliers win (ties: the
+ * lowest hypothesis), then a least-squares refit on the winner's inliers (refine = 1).  The output is a pure function of (points,
+ * seed, budget, threshold).  d_mask: capacity bytes, 1 for the winner's inliers, 0 elsewhere (rows at or beyond the count too).
+ * No host synchronisation inside (the matcher's scratch grows with a device-wide wait the first time larger sizes arrive). */
+typedef struct efx_ransac_params {
+    int hypotheses;                 /* 2048; 1 .. 65536 */
+    float threshold;                /* 3.0f: reprojection error in pixels, finite and > 0 */
+    unsigned long long seed;        /* 0 */
+    int refine;                     /* 1: least-squares refit on the inliers */
+} efx_ransac_params;
+typedef struct efx_homography {     /* written on the device, one per pair */
+    double H[9];                    /* row-major, H[8] == 1; all 0 when there is no model */
+    int ninliers, hypothesis;       /* the winner's inlier count and index (-1: no model) */
+    int valid_hypotheses, refined;  /* hypotheses that passed the subset check; 1 if H is the refit */
+} efx_homography;
+void efx_default_ransac_params(efx_ransac_params* p);
+int efx_match_homography_async(efx_matcher* m,
+                               const void* d_kps_q, size_t q_kps_pitch, int q_kps_capacity,
+                               const void* d_kps_t, size_t t_kps_pitch, int t_kps_capacity,
+                               const int* d_matches, const int* d_nmatches, int capacity,
+                               const efx_ransac_params* p, efx_homography* d_result, uint8_t* d_mask, void* stream);
+/* npairs pairs in one call: the arguments above as tables of npairs pointers (d_nmatches may be NULL: every count = capacity).
+ * Seven launches (five without the refit) per chain of up to EFX_MAX_BATCH = 16 pairs (pair = blockIdx.z); every pair's output
+ * equals efx_match_homography_async's on it, bit for bit. */
+int efx_match_homography_batch_async(efx_matcher* m, int npairs,
+                                     const void* const* d_kps_q, size_t q_kps_pitch, int q_kps_capacity,
+                                     const void* const* d_kps_t, size_t t_kps_pitch, int t_kps_capacity,
+                                     const int* const* d_matches, const int* const* d_nmatches, int capacity,
+                                     const efx_ransac_params* p, efx_homography* const* d_result, uint8_t* const* d_mask,
+                                     void* stream);
+
 /* Batched variant (SURVEY 8b "batched variants (..., nframes) for roofline-sized launches"; the loop of
  * samples/sample_image_sequence.cpp:70-105): nframes independent frames of one size in one call.  Frame i belongs to context
  * ctxs[i % nctx] and stream streams[i % nctx]; the frames of ONE context go through ONE launch of every kernel of the path (frame =
