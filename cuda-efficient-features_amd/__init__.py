@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "efx_matcher_create", "efx_matcher_destroy", "efx_matcher_last_error", "efx_match_knn2_async",
     "efx_match_crosscheck_async", "efx_match_mutual_async", "efx_match_mutual_batch_async",
     "efx_default_ransac_params", "efx_match_homography_async", "efx_match_homography_batch_async",
+    "efx_default_guided_params", "efx_match_guided_async", "efx_match_guided_batch_async",
     "efx_detect_and_compute_batch_async", "efx_detect_and_compute_masked_async", "efx_compute_provided_async", "efx_detect_and_compute_ex",
     "efx_ic_angles_async", "efx_ic_angles", "efx_descriptors_to_csv",
     "efx_cvt_gray_async", "efx_host_alloc", "efx_host_free", "efx_uploader_create", "efx_uploader_destroy",
@@ -67,6 +68,11 @@ class Params(C.Structure):
 class RansacParams(C.Structure):
     """efx_ransac_params (include/efx.h)"""
     _fields_ = [("hypotheses", C.c_int), ("threshold", C.c_float), ("seed", C.c_ulonglong), ("refine", C.c_int)]
+
+
+class GuidedParams(C.Structure):
+    """efx_guided_params (include/efx.h)"""
+    _fields_ = [("radius", C.c_float), ("max_octave_diff", C.c_int), ("ratio", C.c_double), ("width", C.c_int), ("height", C.c_int)]
 
 
 HOMOGRAPHY_BYTES = 88          # sizeof(efx_homography): double H[9]; int ninliers, hypothesis, valid_hypotheses, refined
@@ -163,6 +169,14 @@ def lib():
         L.efx_match_homography_batch_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
                                                        C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RansacParams), C.c_void_p,
                                                        C.c_void_p, C.c_void_p]
+        L.efx_default_guided_params.restype = None
+        L.efx_default_guided_params.argtypes = [C.POINTER(GuidedParams)]
+        L.efx_match_guided_async.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                             C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
+                                             C.POINTER(GuidedParams), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.efx_match_guided_batch_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
+                                                   C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                                   C.c_int, C.c_void_p, C.POINTER(GuidedParams), C.c_void_p, C.c_void_p, C.c_void_p]
         L.efx_detect_and_compute_batch_async.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t,
                                                          C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         L.efx_detect_and_compute_masked_async.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t,
@@ -814,6 +828,62 @@ class BFMatcher:
         return b.matches, b.nmatches
 
     @staticmethod
+    def _guided(radius, max_octave_diff, ratio, width, height):
+        p = GuidedParams()
+        p.radius, p.max_octave_diff, p.ratio, p.width, p.height = float(radius), int(max_octave_diff), float(ratio), int(width), int(height)
+        return p
+
+    @staticmethod
+    def _prior(t):
+        """A device efx_homography record: findHomography's H (a view of the start of its 88-byte result buffer),
+        homographyRecord's, or None (identity)."""
+        import torch
+        if t is None:
+            return None
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.data_ptr() % 8 == 0
+                and t.untyped_storage().nbytes() - t.storage_offset() * t.element_size() >= HOMOGRAPHY_BYTES):
+            raise EfxError(-1, "a prior must be the H of findHomography / homographyRecord (an 88-byte device record), or None")
+        return t
+
+    @staticmethod
+    def _guided_sides(q, kq, t, kt):
+        if q.shape[1] != t.shape[1]:
+            raise EfxError(-1, "query and train descriptors differ in size")
+        if kq.shape[1] != q.shape[0] or kt.shape[1] != t.shape[0]:
+            raise EfxError(-1, "a keypoint matrix has one column per descriptor row")
+
+    def matchGuided(self, query, kps_q, train, kps_t, prior=None, radius=16.0, max_octave_diff=-1, ratio=0.9, width=0, height=0,
+                    nq=None, nt=None, stream=None):
+        """Guided (spatially gated) mutual matching on the device: matchMutual with both directions restricted to the
+        pairs whose train keypoint lies within `radius` pixels (square window, inclusive) of the position `prior` predicts for the
+        query keypoint, and whose octaves differ by at most max_octave_diff (-1: off).  kps_q / kps_t: the 5 x capacity keypoint
+        matrices of the descriptor matrices; prior: the H tensor findHomography returned (used straight from the device), a
+        homographyRecord, or None (identity); width / height: a frame size hint that never changes the result.  Returns (matches,
+        nmatches) as matchMutual.  No host sync."""
+        import torch
+        q, t = self._mdesc(query), self._mdesc(train)
+        kq, kt = self._kps(kps_q), self._kps(kps_t)
+        self._guided_sides(q, kq, t, kt)
+        cq, ct, pr = self._count(nq), self._count(nt), self._prior(prior)
+        p = self._guided(radius, max_octave_diff, ratio, width, height)
+        out = torch.empty((max(q.shape[0], 1), 3), dtype=torch.int32, device=q.device)
+        n = torch.empty((1,), dtype=torch.int32, device=q.device)
+        self._check(lib().efx_match_guided_async(self._h, q.data_ptr(), self._pitch(q), cq.data_ptr() if cq is not None else None,
+                                                 q.shape[0], kq.data_ptr(), kq.stride(0) * 4,
+                                                 t.data_ptr(), self._pitch(t), ct.data_ptr() if ct is not None else None,
+                                                 t.shape[0], kt.data_ptr(), kt.stride(0) * 4, q.shape[1],
+                                                 pr.data_ptr() if pr is not None else None, C.byref(p), out.data_ptr(), n.data_ptr(),
+                                                 _stream_ptr(stream)))
+        return out[:q.shape[0]], n
+
+    def matchGuidedBatch(self, queries, kps_qs, trains, kps_ts, priors=None, radius=16.0, max_octave_diff=-1, ratio=0.9, width=0,
+                         height=0, nqs=None, nts=None, stream=None):
+        """matchGuided over npairs pairs in one call (GuidedBatch, run once): lists of (matches, nmatches)."""
+        b = GuidedBatch(self, queries, kps_qs, trains, kps_ts, priors, radius, max_octave_diff, ratio, width, height, nqs, nts, stream)
+        b.run()
+        return b.matches, b.nmatches
+
+    @staticmethod
     def _kps(t):
         import torch
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == 5
@@ -909,6 +979,76 @@ class MutualBatch:
         n, qp, qcap, tp, tcap, db, ratio = self._args
         matcher._check(lib().efx_match_mutual_batch_async(matcher._h, n, self._q, qp, self._nq, qcap, self._t, tp, self._nt, tcap,
                                                           db, ratio, self._m, self._n, _stream_ptr(stream)))
+
+
+class GuidedBatch:
+    """efx_match_guided_batch_async with prepared pointer tables (like MutualBatch): pair i matches queries[i] (keypoints kps_qs[i])
+    against trains[i] (kps_ts[i]) inside the windows priors[i] predicts (None, or None entries: identity), with optional device counts
+    nqs[i] / nts[i]; the matrices of one side have one shape and pitch.  The outputs are allocated here (matches[i]: q_capacity x 3
+    int32, nmatches[i]: 1 int32); run() crosses the ABI once and may be repeated."""
+
+    def __init__(self, matcher, queries, kps_qs, trains, kps_ts, priors=None, radius=16.0, max_octave_diff=-1, ratio=0.9, width=0,
+                 height=0, nqs=None, nts=None, stream=None):
+        import torch
+        n = len(queries)
+        if len(trains) != n or len(kps_qs) != n or len(kps_ts) != n or (nqs is not None and len(nqs) != n) or \
+                (nts is not None and len(nts) != n) or (priors is not None and len(priors) != n):
+            raise EfxError(-1, "one train matrix, keypoint matrix pair (count, prior) per query matrix")
+        qs = [BFMatcher._mdesc(q) for q in queries]
+        ts = [BFMatcher._mdesc(t) for t in trains]
+        kq = [BFMatcher._kps(a) for a in kps_qs]
+        kt = [BFMatcher._kps(a) for a in kps_ts]
+        for i in range(n):
+            BFMatcher._guided_sides(qs[i], kq[i], ts[i], kt[i])
+        for a in qs + ts:
+            if a.shape[1] != qs[0].shape[1]:
+                raise EfxError(-1, "every descriptor matrix of a batch has one row size")
+        for group in (qs, ts):
+            for a in group:
+                if a.shape[0] != group[0].shape[0] or BFMatcher._pitch(a) != BFMatcher._pitch(group[0]):
+                    raise EfxError(-1, "the query (train) matrices of a batch have one capacity and pitch")
+        for group in (kq, kt):
+            for a in group:
+                if a.stride(0) != group[0].stride(0):
+                    raise EfxError(-1, "the query (train) keypoint matrices of a batch have one pitch")
+        cq = [BFMatcher._count(c) for c in nqs] if nqs is not None else None
+        ct = [BFMatcher._count(c) for c in nts] if nts is not None else None
+        pr = [BFMatcher._prior(a) for a in priors] if priors is not None else None
+        qcap = qs[0].shape[0] if n else 0
+        dev = qs[0].device if n else None
+        self.matches = [torch.empty((max(qcap, 1), 3), dtype=torch.int32, device=dev)[:qcap] for _ in range(n)]
+        self.nmatches = [torch.empty((1,), dtype=torch.int32, device=dev) for _ in range(n)]
+        self._params = BFMatcher._guided(radius, max_octave_diff, ratio, width, height)
+        self._keep = (matcher, qs, ts, kq, kt, cq, ct, pr, stream)
+        P = C.c_void_p
+        k = max(n, 1)
+
+        def table(items):
+            return (P * k)(*[P(a.data_ptr()) if a is not None else P() for a in items]) if items is not None else None
+        self._q, self._t, self._kq, self._kt = table(qs), table(ts), table(kq), table(kt)
+        self._nq, self._nt, self._pr = table(cq), table(ct), table(pr)
+        self._m, self._n = table(self.matches), table(self.nmatches)
+        self._args = (n, BFMatcher._pitch(qs[0]) if n else 32, qcap, kq[0].stride(0) * 4 if n else 0,
+                      BFMatcher._pitch(ts[0]) if n else 32, ts[0].shape[0] if n else 0, kt[0].stride(0) * 4 if n else 0,
+                      qs[0].shape[1] if n else 32)
+
+    def run(self):
+        matcher, stream = self._keep[0], self._keep[8]
+        n, qp, qcap, kqp, tp, tcap, ktp, db = self._args
+        matcher._check(lib().efx_match_guided_batch_async(matcher._h, n, self._q, qp, self._nq, qcap, self._kq, kqp, self._t, tp, self._nt,
+                                                          tcap, self._kt, ktp, db, self._pr, C.byref(self._params), self._m, self._n,
+                                                          _stream_ptr(stream)))
+
+
+def homographyRecord(H, hypothesis=0, ninliers=0, device="cuda"):
+    """A device efx_homography record holding the 3 x 3 model H (hypothesis < 0: "no model"): the H view of its 88 bytes, usable as a
+    prior of matchGuided like the H findHomography returns."""
+    import torch
+    rec = np.zeros(HOMOGRAPHY_BYTES, np.uint8)
+    rec[:72] = np.ascontiguousarray(np.asarray(H, np.float64).reshape(9)).view(np.uint8)
+    rec[72:].view(np.int32)[:] = (int(ninliers), int(hypothesis), 0, 0)
+    buf = torch.from_numpy(rec).to(device)
+    return buf[:72].view(torch.float64).view(3, 3)
 
 
 class HomographyBatch:

@@ -17,6 +17,16 @@ hipError_t efx_launch_mutual(int npairs, const uint8_t* const* q, const uint8_t*
                              size_t q_pitch, size_t t_pitch, int q_cap, int t_cap, int desc_bytes, double ratio,
                              int* const* out, int* const* nout, int path, int nchunks,
                              void* partial, void* knn, void* flags, void* wgcount, hipStream_t stream);
+hipError_t efx_launch_mutual_filter(int npairs, const int* const* nq, int q_cap, int cap, double ratio, int* const* out, int* const* nout,
+                                    void* knn, void* flags, void* wgcount, hipStream_t stream);
+// guided_kernels.hip
+void efx_guided_grid(float radius, int width, int height, int* x0, int* y0, int* edge, int* gw, int* gh);
+size_t efx_guided_scratch(int nbins, int rows, int ncells, int desc_bytes);
+hipError_t efx_launch_guided_search(int nbins, const uint8_t* const* desc, const size_t* dpitch, const uint8_t* const* kps,
+                                    const size_t* kpitch, const int* const* cnt, const int* cap, const efx_homography* const* prior,
+                                    int npairs, const int* qbin, const int* tbin, int cap_max, int desc_bytes,
+                                    float radius, int max_octave_diff, int width, int height,
+                                    void* scratch, void* knn, hipStream_t stream);
 // homography_kernels.hip
 size_t efx_homography_scratch(int npairs, int cap, int hyps);
 hipError_t efx_launch_homography(int npairs, const void* const* kq, const void* const* kt, const int* const* m, const int* const* nm,
@@ -411,10 +421,10 @@ struct efx_matcher {
     bool no_mfma = getenv("EFX_MATCH_NO_MFMA") != nullptr;        // variant knob (tests: force the popcount kernel), read when the matcher is created
     bool no_fp4 = getenv("EFX_MATCH_NO_FP4") != nullptr;          // ... the int8 matrix-core kernel instead of the FP4 one
     // expanded matrices (matrix cores), per-chunk best two, knnMatch lists (crossCheck, mutual), mutual flags + workgroup counts,
-    // homography chains (gathered rows, hypothesis coefficients and counts)
-    DevBuf x, part, knn, flag, hom;
+    // homography chains (gathered rows, hypothesis coefficients and counts), guided chains (cell tables and cell-ordered rows)
+    DevBuf x, part, knn, flag, hom, guided;
     std::string err;
-    ~efx_matcher() { x.release(); part.release(); knn.release(); flag.release(); hom.release(); }
+    ~efx_matcher() { x.release(); part.release(); knn.release(); flag.release(); hom.release(); guided.release(); }
 };
 
 struct efx_context {
@@ -2273,6 +2283,110 @@ int efx_match_homography_async(efx_matcher* m,
 {
     return efx_match_homography_batch_async(m, 1, &d_kps_q, q_kps_pitch, q_kps_capacity, &d_kps_t, t_kps_pitch, t_kps_capacity,
                                             &d_matches, &d_nmatches, capacity, p, &d_result, &d_mask, stream);
+}
+
+// ---- guided (spatially gated) mutual matching ----
+void efx_default_guided_params(efx_guided_params* p)
+{
+    if (!p) return;
+    p->radius = 16.0f; p->max_octave_diff = -1; p->ratio = 0.9; p->width = 0; p->height = 0;
+}
+
+int efx_match_guided_batch_async(efx_matcher* m, int npairs,
+                                 const uint8_t* const* d_query, size_t q_pitch, const int* const* d_nq, int q_capacity,
+                                 const void* const* d_kps_q, size_t q_kps_pitch,
+                                 const uint8_t* const* d_train, size_t t_pitch, const int* const* d_nt, int t_capacity,
+                                 const void* const* d_kps_t, size_t t_kps_pitch,
+                                 int desc_bytes, const efx_homography* const* d_prior, const efx_guided_params* p,
+                                 int* const* d_matches, int* const* d_nmatches, void* stream)
+{
+    if (!m) return EFX_ERR_BAD_ARG;
+    if (npairs < 0) return set_err(m->err, EFX_ERR_BAD_ARG, "negative pair count");
+    if (!p) return set_err(m->err, EFX_ERR_BAD_ARG, "null parameters");
+    if (!isfinite(p->radius) || !(p->radius > 0.f)) return set_err(m->err, EFX_ERR_BAD_ARG, "radius must be finite and > 0");
+    if (!isfinite(p->ratio) || p->ratio < 0.0) return set_err(m->err, EFX_ERR_BAD_ARG, "ratio must be finite and >= 0");
+    if (p->width < 0 || p->height < 0) return set_err(m->err, EFX_ERR_BAD_ARG, "negative frame size hint");
+    const int db = desc_bytes;
+    if (db != 32 && db != 64) return set_err(m->err, EFX_ERR_BAD_ARG, "descriptor size must be 32 or 64 bytes");
+    if (q_capacity < 0 || t_capacity < 0) return set_err(m->err, EFX_ERR_BAD_ARG, "negative capacity");
+    if (npairs == 0) return EFX_OK;
+    if (!d_query || !d_train || !d_kps_q || !d_kps_t || !d_matches || !d_nmatches) return set_err(m->err, EFX_ERR_BAD_ARG, "null pointer table");
+    if (q_pitch < (size_t)db || t_pitch < (size_t)db || ((q_pitch | t_pitch) & 3u))
+        return set_err(m->err, EFX_ERR_BAD_ARG, "descriptor rows must be 4-byte aligned and at least desc_bytes apart");
+    if (q_kps_pitch < 4 * (size_t)q_capacity || t_kps_pitch < 4 * (size_t)t_capacity || ((q_kps_pitch | t_kps_pitch) & 3u))
+        return set_err(m->err, EFX_ERR_BAD_ARG, "keypoint rows must be 4-byte aligned and at least 4 x capacity bytes apart");
+    for (int i = 0; i < npairs; i++) {
+        if ((q_capacity > 0 && (!d_query[i] || !d_kps_q[i])) || (t_capacity > 0 && (!d_train[i] || !d_kps_t[i])))
+            return set_err(m->err, EFX_ERR_BAD_ARG, "null descriptors or keypoints");
+        if (((uintptr_t)d_query[i] | (uintptr_t)d_train[i] | (uintptr_t)d_kps_q[i] | (uintptr_t)d_kps_t[i]) & 3u)
+            return set_err(m->err, EFX_ERR_BAD_ARG, "descriptors and keypoints must be 4-byte aligned");
+        if (d_prior && ((uintptr_t)d_prior[i] & 7u)) return set_err(m->err, EFX_ERR_BAD_ARG, "a prior must be 8-byte aligned");
+        if (!d_matches[i] || !d_nmatches[i]) return set_err(m->err, EFX_ERR_BAD_ARG, "null outputs");
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    const int cap = std::max({ q_capacity, t_capacity, 1 });
+    const int chain = std::min(npairs, EFX_MAX_BATCH);
+
+    // A chain's bins: every distinct (descriptors, keypoints, count, capacity, pitches, prior) is sorted into its cells once.  A
+    // train, and a query without a prior, are binned by their own locations: frame i as the train of pair i - 1 and the query of
+    // pair i shares one bin when no prior is given.
+    struct Bin { const uint8_t* desc; size_t dpitch; const uint8_t* kps; size_t kpitch; const int* cnt; int cap; const efx_homography* prior; };
+    auto same = [](const Bin& a, const Bin& b) {
+        return a.desc == b.desc && a.dpitch == b.dpitch && a.kps == b.kps && a.kpitch == b.kpitch && a.cnt == b.cnt && a.cap == b.cap &&
+               a.prior == b.prior;
+    };
+    int gx0, gy0, edge, gw, gh;
+    efx_guided_grid(p->radius, p->width, p->height, &gx0, &gy0, &edge, &gw, &gh);
+    const int nblk = std::max(1, (q_capacity + 255) / 256);
+    const size_t flag_bytes = align_up((size_t)chain * (size_t)std::max(q_capacity, 1), 256);
+    // every block is reserved before the first launch (for the most bins a chain can have): a regrow, the only place this path may
+    // wait on the host, never finds work of THIS call in flight
+    HIP_TRY(m->err, m->guided.reserve(efx_guided_scratch(2 * chain, cap, gw * gh, db)));
+    HIP_TRY(m->err, m->knn.reserve((size_t)(2 * chain) * cap * 16));
+    HIP_TRY(m->err, m->flag.reserve(flag_bytes + (size_t)chain * nblk * 4));
+    for (int p0 = 0; p0 < npairs; p0 += EFX_MAX_BATCH) {
+        const int k = std::min(npairs - p0, EFX_MAX_BATCH);
+        std::vector<Bin> bins;
+        int qbin[EFX_MAX_BATCH], tbin[EFX_MAX_BATCH];
+        const int* nq[EFX_MAX_BATCH];
+        auto place = [&](const Bin& b) {
+            for (size_t i = 0; i < bins.size(); i++) if (same(bins[i], b)) return (int)i;
+            bins.push_back(b);
+            return (int)bins.size() - 1;
+        };
+        for (int i = 0; i < k; i++) {
+            const int pr = p0 + i;
+            nq[i] = d_nq ? d_nq[pr] : nullptr;
+            qbin[i] = place({ d_query[pr], q_pitch, static_cast<const uint8_t*>(d_kps_q[pr]), q_kps_pitch, nq[i], q_capacity,
+                              d_prior ? d_prior[pr] : nullptr });
+            tbin[i] = place({ d_train[pr], t_pitch, static_cast<const uint8_t*>(d_kps_t[pr]), t_kps_pitch, d_nt ? d_nt[pr] : nullptr,
+                              t_capacity, nullptr });
+        }
+        const int nb = (int)bins.size();
+        const uint8_t* desc[2 * EFX_MAX_BATCH]; const uint8_t* kps[2 * EFX_MAX_BATCH]; size_t dp[2 * EFX_MAX_BATCH], kp[2 * EFX_MAX_BATCH];
+        const int* cnt[2 * EFX_MAX_BATCH]; int cp[2 * EFX_MAX_BATCH]; const efx_homography* prior[2 * EFX_MAX_BATCH];
+        for (int b = 0; b < nb; b++) {
+            desc[b] = bins[b].desc; dp[b] = bins[b].dpitch; kps[b] = bins[b].kps; kp[b] = bins[b].kpitch; cnt[b] = bins[b].cnt;
+            cp[b] = bins[b].cap; prior[b] = bins[b].prior;
+        }
+        hipError_t e = efx_launch_guided_search(nb, desc, dp, kps, kp, cnt, cp, prior, k, qbin, tbin, cap, db, p->radius, p->max_octave_diff,
+                                                p->width, p->height, m->guided.p, m->knn.p, st);
+        if (e == hipSuccess)
+            e = efx_launch_mutual_filter(k, nq, q_capacity, cap, p->ratio, d_matches + p0, d_nmatches + p0, m->knn.p, m->flag.p,
+                                         static_cast<uint8_t*>(m->flag.p) + flag_bytes, st);
+        if (e != hipSuccess) return set_err(m->err, EFX_ERR_HIP, "guided match launch failed: %s", hipGetErrorString(e));
+    }
+    return EFX_OK;
+}
+
+int efx_match_guided_async(efx_matcher* m,
+                           const uint8_t* d_query, size_t q_pitch, const int* d_nq, int q_capacity, const void* d_kps_q, size_t q_kps_pitch,
+                           const uint8_t* d_train, size_t t_pitch, const int* d_nt, int t_capacity, const void* d_kps_t, size_t t_kps_pitch,
+                           int desc_bytes, const efx_homography* d_prior, const efx_guided_params* p,
+                           int* d_matches, int* d_nmatches, void* stream)
+{
+    return efx_match_guided_batch_async(m, 1, &d_query, q_pitch, &d_nq, q_capacity, &d_kps_q, q_kps_pitch, &d_train, t_pitch, &d_nt,
+                                        t_capacity, &d_kps_t, t_kps_pitch, desc_bytes, &d_prior, p, &d_matches, &d_nmatches, stream);
 }
 
 int efx_level_geometry(const efx_context* ctx, int rows, int cols, int level, int* lrows, int* lcols, float* scale)

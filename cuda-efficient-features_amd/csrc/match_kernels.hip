@@ -570,3 +570,22 @@ hipError_t efx_launch_mutual(int npairs, const uint8_t* const* q, const uint8_t*
     hipLaunchKernelGGL(mutual_compact_kernel, fgrid, dim3(256), 0, stream, J, (const uint8_t*)flags, (const int*)wgcount, nblk);
     return hipGetLastError();
 }
+
+// The flag + compact half of the chain above on knnMatch lists another search wrote (guided matching, guided_kernels.hip): knn
+// holds idx, then dist, 2 npairs x cap x 2 ints each, jobs 2 p (query -> train) and 2 p + 1 (train -> query) of pair p
+hipError_t efx_launch_mutual_filter(int npairs, const int* const* nq, int q_cap, int cap, double ratio, int* const* out, int* const* nout,
+                                    void* knn, void* flags, void* wgcount, hipStream_t stream)
+{
+    if (npairs <= 0) return hipSuccess;
+    if (npairs > EFX_MAX_BATCH) return hipErrorInvalidValue;
+    KnnJobs J = {};
+    for (int p = 0; p < npairs; p++) { J.nq[p] = nq[p]; J.out[p] = out[p]; J.nout[p] = nout[p]; }
+    J.q_cap = q_cap; J.cap = cap;
+    J.idx = static_cast<int*>(knn);
+    J.dist = J.idx + (size_t)(2 * npairs) * 2 * J.cap;
+    const int nblk = (q_cap + 255) / 256 > 0 ? (q_cap + 255) / 256 : 1;
+    const dim3 fgrid((unsigned)nblk, 1, (unsigned)npairs);
+    hipLaunchKernelGGL(mutual_flag_kernel, fgrid, dim3(256), 0, stream, J, ratio, static_cast<uint8_t*>(flags), static_cast<int*>(wgcount), nblk);
+    hipLaunchKernelGGL(mutual_compact_kernel, fgrid, dim3(256), 0, stream, J, (const uint8_t*)flags, (const int*)wgcount, nblk);
+    return hipGetLastError();
+}

@@ -384,6 +384,67 @@ public:
         if (k > 0 && hipMemcpy(h.data(), d + 1, h.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) throw Exception(EFX_ERR_HIP, "download failed");
         for (int i = 0; i < k; i++) matches.push_back(DMatch{ h[3 * i], h[3 * i + 1], h[3 * i + 2] });
     }
+    // Guided (spatially gated) mutual matching: matchMutualAsync with both directions restricted to the trains inside
+    // the window of params->radius around the position d_prior (a device efx_homography, query -> train, e.g. findHomographyAsync's
+    // d_result; nullptr: identity) predicts for a query.  kpsQ / kpsT: the 5 x capacity keypoint matrices of the descriptors.
+    void matchGuidedAsync(const DeviceMatrix& query, const int* d_nq, const DeviceMatrix& kpsQ, const DeviceMatrix& train, const int* d_nt,
+                          const DeviceMatrix& kpsT, int descBytes, const efx_homography* d_prior, DeviceMatrix& matches, int* d_nmatches,
+                          const efx_guided_params* params = nullptr, hipStream_t stream = nullptr)
+    {
+        const efx_guided_params p = guided_or_default(params);
+        matches.create(query.rows > 0 ? query.rows : 1, 3, 4);
+        check(efx_match_guided_async(m_, static_cast<const uint8_t*>(query.data()), query.step, d_nq, query.rows, kpsQ.data(), kpsQ.step,
+                                     static_cast<const uint8_t*>(train.data()), train.step, d_nt, train.rows, kpsT.data(), kpsT.step,
+                                     descBytes, d_prior, &p, static_cast<int*>(matches.data()), d_nmatches, stream));
+    }
+    // pairs i in one call (a memset and seven launches per 16 pairs); the matrices of one side have one shape; d_prior may be empty
+    void matchGuidedBatchAsync(const std::vector<const DeviceMatrix*>& query, const std::vector<const int*>& d_nq,
+                               const std::vector<const DeviceMatrix*>& kpsQ,
+                               const std::vector<const DeviceMatrix*>& train, const std::vector<const int*>& d_nt,
+                               const std::vector<const DeviceMatrix*>& kpsT, int descBytes,
+                               const std::vector<const efx_homography*>& d_prior, std::vector<DeviceMatrix>& matches,
+                               const std::vector<int*>& d_nmatches, const efx_guided_params* params = nullptr, hipStream_t stream = nullptr)
+    {
+        const size_t n = query.size();
+        if (train.size() != n || d_nq.size() != n || d_nt.size() != n || kpsQ.size() != n || kpsT.size() != n || d_nmatches.size() != n ||
+            (!d_prior.empty() && d_prior.size() != n))
+            throw Exception(EFX_ERR_BAD_ARG, "one train matrix, keypoint matrix pair, count pair, prior and output per query matrix");
+        if (n == 0) return;
+        const efx_guided_params p = guided_or_default(params);
+        matches.resize(n);
+        std::vector<const uint8_t*> q(n), t(n);
+        std::vector<const void*> kq(n), kt(n);
+        std::vector<int*> out(n);
+        for (size_t i = 0; i < n; i++) {
+            if (query[i]->rows != query[0]->rows || query[i]->step != query[0]->step || train[i]->rows != train[0]->rows ||
+                train[i]->step != train[0]->step || kpsQ[i]->step != kpsQ[0]->step || kpsT[i]->step != kpsT[0]->step)
+                throw Exception(EFX_ERR_BAD_ARG, "the query (train) matrices of a batch have one shape");
+            matches[i].create(query[0]->rows > 0 ? query[0]->rows : 1, 3, 4);
+            q[i] = static_cast<const uint8_t*>(query[i]->data()); t[i] = static_cast<const uint8_t*>(train[i]->data());
+            kq[i] = kpsQ[i]->data(); kt[i] = kpsT[i]->data();
+            out[i] = static_cast<int*>(matches[i].data());
+        }
+        check(efx_match_guided_batch_async(m_, (int)n, q.data(), query[0]->step, d_nq.data(), query[0]->rows, kq.data(), kpsQ[0]->step,
+                                           t.data(), train[0]->step, d_nt.data(), train[0]->rows, kt.data(), kpsT[0]->step, descBytes,
+                                           d_prior.empty() ? nullptr : d_prior.data(), &p, out.data(), d_nmatches.data(), stream));
+    }
+    // host convenience: every row of both sides, the kept pairs downloaded (one stream synchronisation)
+    void matchGuided(const DeviceMatrix& query, const DeviceMatrix& kpsQ, const DeviceMatrix& train, const DeviceMatrix& kpsT, int descBytes,
+                     const efx_homography* d_prior, std::vector<DMatch>& matches, const efx_guided_params* params = nullptr,
+                     hipStream_t stream = nullptr)
+    {
+        matches.clear();
+        ncount_.create(1, 1, 4);
+        int* d = static_cast<int*>(ncount_.data());
+        matchGuidedAsync(query, nullptr, kpsQ, train, nullptr, kpsT, descBytes, d_prior, gmatches_, d, params, stream);
+        int k = 0;
+        if (hipStreamSynchronize(stream) != hipSuccess || hipMemcpy(&k, d, 4, hipMemcpyDeviceToHost) != hipSuccess)
+            throw Exception(EFX_ERR_HIP, "download failed");
+        std::vector<int> h((size_t)3 * k);
+        if (k > 0 && hipMemcpy(h.data(), gmatches_.data(), h.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
+            throw Exception(EFX_ERR_HIP, "download failed");
+        for (int i = 0; i < k; i++) matches.push_back(DMatch{ h[3 * i], h[3 * i + 1], h[3 * i + 2] });
+    }
     // cv::findHomography(src, dst, RANSAC) on matched keypoints, on the device: kpsQ / kpsT are 5 x capacity keypoint
     // matrices (row 0 is read), matches the {queryIdx, trainIdx, distance} rows of matchMutualAsync with the count d_nmatches (a
     // device int, nullptr: every row).  d_result (device) receives the model, mask matches.rows bytes.  No host synchronisation.
@@ -444,7 +505,13 @@ private:
         efx_default_ransac_params(&p);
         return params ? *params : p;
     }
-    DeviceMatrix hres_, hmask_;
+    static efx_guided_params guided_or_default(const efx_guided_params* params)
+    {
+        efx_guided_params p;
+        efx_default_guided_params(&p);
+        return params ? *params : p;
+    }
+    DeviceMatrix hres_, hmask_, gmatches_, ncount_;
     void check(int rc) const { if (rc != EFX_OK) throw Exception(rc, efx_matcher_last_error(m_)); }
     efx_matcher* m_ = nullptr;
     bool cross_;

@@ -310,6 +310,50 @@ int efx_match_homography_batch_async(efx_matcher* m, int npairs,
                                      const efx_ransac_params* p, efx_homography* const* d_result, uint8_t* const* d_mask,
                                      void* stream);
 
+/* Guided (spatially gated) mutual matching on the device, DESIGN.md spec S17: the filter of efx_match_mutual_async with both knnMatch
+ * directions restricted to the candidate pairs C.  Pair (i, j) is in C iff train j lies in the square window of `radius` pixels
+ * (inclusive) around the position predicted for query i, and -- with max_octave_diff >= 0 -- |octave_i - octave_j| <=
+ * max_octave_diff.  d_kps_q / d_kps_t are the 5xN keypoint matrices of the two descriptor matrices (column i belongs to descriptor
+ * row i; the descriptor capacity is the keypoint capacity; the LOCATION row is read, the OCTAVE row only with the octave gate).
+ * d_prior: a device efx_homography mapping query to train, e.g. what efx_match_homography_async wrote earlier on the stream (no
+ * host round trip); NULL: identity.  The prediction, in double without fused multiply-adds: X = (H0 x + H1 y) + H2, Y = (H3 x +
+ * H4 y) + H5, W = (H6 x + H7 y) + H8, (px, py) = (X / W, Y / W); a query with !(W > 0) or a non-finite prediction has no
+ * candidates; a prior with hypothesis < 0 (no model) gives no matches.  The gate  fabs((double)x'_j - px) <= (double)radius  (and
+ * the same in y) is evaluated from the query side only, so both directions use one set C.  m12(i): the best two trains among
+ * { j : (i, j) in C }, m21(j): the best two queries among { i : (i, j) in C } (distance = differing bits, ties to the lower index, -1
+ * where missing); then exactly the three checks of efx_match_mutual_async.  Counts, output and ordering as there: the result feeds
+ * efx_match_homography_async unchanged.  width / height are a hint ("locations lie in [0, width) x [0, height)", 0: unknown) that
+ * sizes the cell grid and never changes the result.  With no prior, the octave gate off and radius >= 65535 the output equals
+ * efx_match_mutual_async's; for any parameters every row of that output whose pair passes the gate is a row of this one.
+ * The work is proportional to the candidates the windows hold (about a dozen per keypoint in a frame), not to nq x nt; there is no
+ * cap on candidates per window.  No host synchronisation inside (the matcher's scratch grows with a device-wide wait the first
+ * time larger sizes arrive). */
+typedef struct efx_guided_params {
+    float radius;                   /* 16.0f: half the window edge in pixels, finite and > 0 */
+    int max_octave_diff;            /* -1: octave gate off */
+    double ratio;                   /* 0.9: the ratio test of S15, finite and >= 0 */
+    int width, height;              /* 0, 0: frame size hint, >= 0 */
+} efx_guided_params;
+void efx_default_guided_params(efx_guided_params* p);
+int efx_match_guided_async(efx_matcher* m,
+                           const uint8_t* d_query, size_t q_pitch, const int* d_nq, int q_capacity, const void* d_kps_q, size_t q_kps_pitch,
+                           const uint8_t* d_train, size_t t_pitch, const int* d_nt, int t_capacity, const void* d_kps_t, size_t t_kps_pitch,
+                           int desc_bytes, const efx_homography* d_prior, const efx_guided_params* p,
+                           int* d_matches, int* d_nmatches, void* stream);
+/* npairs pairs in one call: the arguments above as tables of npairs pointers (d_nq, d_nt and d_prior may be NULL, or hold NULL
+ * entries).  A memset and seven launches per chain of up to EFX_MAX_BATCH = 16 pairs (pair = blockIdx.z), more pairs in several chains; every
+ * pair's output equals efx_match_guided_async's on it, bit for bit.  A matrix that appears on the same terms in several pairs of a
+ * chain (same descriptors, keypoints, count, capacity and prior; a query without a prior is on the terms of a train) is sorted into
+ * its cells once.  Scratch is bounded by one chain: at most 32 sorted matrices of max(q_capacity, t_capacity) rows of 48 +
+ * desc_bytes bytes, plus 8 bytes per grid cell and matrix (at most 2^18 cells). */
+int efx_match_guided_batch_async(efx_matcher* m, int npairs,
+                                 const uint8_t* const* d_query, size_t q_pitch, const int* const* d_nq, int q_capacity,
+                                 const void* const* d_kps_q, size_t q_kps_pitch,
+                                 const uint8_t* const* d_train, size_t t_pitch, const int* const* d_nt, int t_capacity,
+                                 const void* const* d_kps_t, size_t t_kps_pitch,
+                                 int desc_bytes, const efx_homography* const* d_prior, const efx_guided_params* p,
+                                 int* const* d_matches, int* const* d_nmatches, void* stream);
+
 /* Batched variant (SURVEY 8b "batched variants (..., nframes) for roofline-sized launches"; the loop of
  * samples/sample_image_sequence.cpp:70-105): nframes independent frames of one size in one call.  Frame i belongs to context
  * ctxs[i % nctx] and stream streams[i % nctx]; the frames of ONE context go through ONE launch of every kernel of the path (frame =
