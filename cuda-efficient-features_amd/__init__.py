@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "efx_matcher_create", "efx_matcher_destroy", "efx_matcher_last_error", "efx_match_knn2_async",
     "efx_match_crosscheck_async", "efx_match_mutual_async", "efx_match_mutual_batch_async",
     "efx_default_ransac_params", "efx_match_homography_async", "efx_match_homography_batch_async",
+    "efx_match_fundamental_async", "efx_match_fundamental_batch_async",
     "efx_default_guided_params", "efx_match_guided_async", "efx_match_guided_batch_async",
     "efx_detect_and_compute_batch_async", "efx_detect_and_compute_masked_async", "efx_compute_provided_async", "efx_detect_and_compute_ex",
     "efx_ic_angles_async", "efx_ic_angles", "efx_descriptors_to_csv",
@@ -76,6 +77,7 @@ class GuidedParams(C.Structure):
 
 
 HOMOGRAPHY_BYTES = 88          # sizeof(efx_homography): double H[9]; int ninliers, hypothesis, valid_hypotheses, refined
+FUNDAMENTAL_BYTES = 88         # sizeof(efx_fundamental): double F[9] and the same four ints
 
 
 class LevelStats(C.Structure):
@@ -169,6 +171,8 @@ def lib():
         L.efx_match_homography_batch_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
                                                        C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RansacParams), C.c_void_p,
                                                        C.c_void_p, C.c_void_p]
+        L.efx_match_fundamental_async.argtypes = L.efx_match_homography_async.argtypes
+        L.efx_match_fundamental_batch_async.argtypes = L.efx_match_homography_batch_async.argtypes
         L.efx_default_guided_params.restype = None
         L.efx_default_guided_params.argtypes = [C.POINTER(GuidedParams)]
         L.efx_match_guided_async.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
@@ -836,11 +840,12 @@ class BFMatcher:
     @staticmethod
     def _prior(t):
         """A device efx_homography record: findHomography's H (a view of the start of its 88-byte result buffer),
-        homographyRecord's, or None (identity)."""
+        homographyRecord's, or None (identity).  The F of findFundamental has the same layout but predicts a line, not a point: it
+        carries a mark and is refused."""
         import torch
         if t is None:
             return None
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.data_ptr() % 8 == 0
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.data_ptr() % 8 == 0 and not getattr(t, "_efx_fundamental", False)
                 and t.untyped_storage().nbytes() - t.storage_offset() * t.element_size() >= HOMOGRAPHY_BYTES):
             raise EfxError(-1, "a prior must be the H of findHomography / homographyRecord (an 88-byte device record), or None")
         return t
@@ -936,6 +941,31 @@ class BFMatcher:
         b = HomographyBatch(self, kps_qs, kps_ts, matches, nmatches, threshold, hypotheses, seed, refine, stream)
         b.run()
         return b.H, b.info, b.mask
+
+    def findFundamental(self, kps_q, kps_t, matches, nmatches=None, threshold=3.0, hypotheses=2048, seed=0, refine=True, stream=None):
+        """cv::findFundamentalMat(src, dst, FM_RANSAC) on matched keypoints, on the device (DESIGN.md S18): the epipolar counterpart
+        of findHomography for scenes with parallax, with the same arguments and outputs.  x'^T F x ~ 0 with x = LOCATION[queryIdx] of
+        kps_q and x' = LOCATION[trainIdx] of kps_t; threshold is the Sampson distance in pixels; every hypothesis draws eight rows,
+        so an all-inlier sample has probability w^8 (w = the inlier share) against findHomography's w^4.  Returns device tensors
+        (F 3 x 3 float64 with its largest entry == 1, info int32[4] = {ninliers, hypothesis (-1: no model), valid_hypotheses,
+        refined}, mask uint8[capacity]).  F is NOT a prior for matchGuided (which predicts a point, not a line) and is refused
+        there.  A planar scene or a purely rotating camera leaves F undetermined: use findHomography for those.  No host sync."""
+        q, t, m = self._kps(kps_q), self._kps(kps_t), self._matches(matches)
+        c = self._count(nmatches)
+        p = self._ransac(threshold, hypotheses, seed, refine)
+        buf, F, info, mask = self._homography_outputs(m.shape[0], m.device)
+        F._efx_fundamental = True
+        self._check(lib().efx_match_fundamental_async(self._h, q.data_ptr(), q.stride(0) * 4, q.shape[1], t.data_ptr(), t.stride(0) * 4,
+                                                      t.shape[1], m.data_ptr(), c.data_ptr() if c is not None else None, m.shape[0],
+                                                      C.byref(p), buf.data_ptr(), mask.data_ptr(), _stream_ptr(stream)))
+        return F, info, mask
+
+    def findFundamentalBatch(self, kps_qs, kps_ts, matches, nmatches=None, threshold=3.0, hypotheses=2048, seed=0, refine=True,
+                             stream=None):
+        """findFundamental over npairs pairs in one call (FundamentalBatch, run once): lists (F, info, mask)."""
+        b = FundamentalBatch(self, kps_qs, kps_ts, matches, nmatches, threshold, hypotheses, seed, refine, stream)
+        b.run()
+        return b.F, b.info, b.mask
 
 
 class MutualBatch:
@@ -1057,6 +1087,8 @@ class HomographyBatch:
     capacity and pitch, every train matrix too, every match list one capacity.  The outputs are allocated here (H[i] 3 x 3 float64,
     info[i] int32[4], mask[i] uint8[capacity]); run() crosses the ABI once and may be repeated."""
 
+    _entry = "efx_match_homography_batch_async"
+
     def __init__(self, matcher, kps_qs, kps_ts, matches, nmatches=None, threshold=3.0, hypotheses=2048, seed=0, refine=True,
                  stream=None):
         n = len(kps_qs)
@@ -1096,8 +1128,23 @@ class HomographyBatch:
     def run(self):
         matcher, stream = self._keep[0], self._keep[5]
         n, qp, qcap, tp, tcap, cap = self._args
-        matcher._check(lib().efx_match_homography_batch_async(matcher._h, n, self._q, qp, qcap, self._t, tp, tcap, self._m, self._n,
-                                                              cap, C.byref(self._params), self._r, self._k, _stream_ptr(stream)))
+        matcher._check(getattr(lib(), self._entry)(matcher._h, n, self._q, qp, qcap, self._t, tp, tcap, self._m, self._n,
+                                                   cap, C.byref(self._params), self._r, self._k, _stream_ptr(stream)))
+
+
+class FundamentalBatch(HomographyBatch):
+    """efx_match_fundamental_batch_async with prepared pointer tables: HomographyBatch with the epipolar model.  The
+    outputs are F[i] (3 x 3 float64, not a prior for matchGuided), info[i] int32[4] and mask[i] uint8[capacity]."""
+
+    _entry = "efx_match_fundamental_batch_async"
+
+    def __init__(self, matcher, kps_qs, kps_ts, matches, nmatches=None, threshold=3.0, hypotheses=2048, seed=0, refine=True,
+                 stream=None):
+        super().__init__(matcher, kps_qs, kps_ts, matches, nmatches, threshold, hypotheses, seed, refine, stream)
+        self.F = self.H
+        del self.H
+        for f in self.F:
+            f._efx_fundamental = True
 
 
 def unpack_keypoints(kps):

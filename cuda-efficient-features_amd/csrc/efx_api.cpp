@@ -27,6 +27,11 @@ hipError_t efx_launch_guided_search(int nbins, const uint8_t* const* desc, const
                                     int npairs, const int* qbin, const int* tbin, int cap_max, int desc_bytes,
                                     float radius, int max_octave_diff, int width, int height,
                                     void* scratch, void* knn, hipStream_t stream);
+// fundamental_kernels.hip
+size_t efx_fundamental_scratch(int npairs, int cap, int hyps);
+hipError_t efx_launch_fundamental(int npairs, const void* const* kq, const void* const* kt, const int* const* m, const int* const* nm,
+                                  int q_cap, int t_cap, int cap, int hyps, float thr, unsigned long long seed, int refine,
+                                  efx_fundamental* const* res, uint8_t* const* mask, void* scratch, hipStream_t stream);
 // homography_kernels.hip
 size_t efx_homography_scratch(int npairs, int cap, int hyps);
 hipError_t efx_launch_homography(int npairs, const void* const* kq, const void* const* kt, const int* const* m, const int* const* nm,
@@ -2282,6 +2287,55 @@ int efx_match_homography_async(efx_matcher* m,
                                const efx_ransac_params* p, efx_homography* d_result, uint8_t* d_mask, void* stream)
 {
     return efx_match_homography_batch_async(m, 1, &d_kps_q, q_kps_pitch, q_kps_capacity, &d_kps_t, t_kps_pitch, t_kps_capacity,
+                                            &d_matches, &d_nmatches, capacity, p, &d_result, &d_mask, stream);
+}
+
+// ---- RANSAC fundamental-matrix verification of matches; the scratch block is the homography chains' ----
+int efx_match_fundamental_batch_async(efx_matcher* m, int npairs,
+                                     const void* const* d_kps_q, size_t q_kps_pitch, int q_kps_capacity,
+                                     const void* const* d_kps_t, size_t t_kps_pitch, int t_kps_capacity,
+                                     const int* const* d_matches, const int* const* d_nmatches, int capacity,
+                                     const efx_ransac_params* p, efx_fundamental* const* d_result, uint8_t* const* d_mask, void* stream)
+{
+    if (!m) return EFX_ERR_BAD_ARG;
+    if (npairs < 0) return set_err(m->err, EFX_ERR_BAD_ARG, "negative pair count");
+    if (!p) return set_err(m->err, EFX_ERR_BAD_ARG, "null parameters");
+    if (p->hypotheses < 1 || p->hypotheses > 65536) return set_err(m->err, EFX_ERR_BAD_ARG, "hypotheses must be 1 .. 65536");
+    if (!isfinite(p->threshold) || !(p->threshold > 0.f)) return set_err(m->err, EFX_ERR_BAD_ARG, "threshold must be finite and > 0");
+    if (q_kps_capacity < 0 || t_kps_capacity < 0 || capacity < 0) return set_err(m->err, EFX_ERR_BAD_ARG, "negative capacity");
+    if (npairs == 0) return EFX_OK;
+    if (!d_kps_q || !d_kps_t || !d_matches || !d_result || !d_mask) return set_err(m->err, EFX_ERR_BAD_ARG, "null pointer table");
+    if (q_kps_pitch < 4 * (size_t)q_kps_capacity || t_kps_pitch < 4 * (size_t)t_kps_capacity)
+        return set_err(m->err, EFX_ERR_BAD_ARG, "keypoint rows must be at least 4 x capacity bytes apart");
+    for (int i = 0; i < npairs; i++) {
+        if ((q_kps_capacity > 0 && !d_kps_q[i]) || (t_kps_capacity > 0 && !d_kps_t[i]) || (capacity > 0 && (!d_matches[i] || !d_mask[i])) ||
+            !d_result[i])
+            return set_err(m->err, EFX_ERR_BAD_ARG, "null pointer");
+        if (((uintptr_t)d_kps_q[i] | (uintptr_t)d_kps_t[i] | (uintptr_t)d_matches[i]) & 3u || (uintptr_t)d_result[i] & 7u)
+            return set_err(m->err, EFX_ERR_BAD_ARG, "keypoints and matches must be 4-byte aligned, results 8-byte aligned");
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    const int chain = std::min(npairs, EFX_MAX_BATCH);
+    const size_t chain_bytes = efx_fundamental_scratch(chain, capacity, p->hypotheses);
+    // reserved before the first launch: a regrow (the only host wait of this path) never finds work of THIS call in flight
+    HIP_TRY(m->err, m->hom.reserve(chain_bytes));
+    for (int p0 = 0; p0 < npairs; p0 += EFX_MAX_BATCH) {
+        const int k = std::min(npairs - p0, EFX_MAX_BATCH);
+        hipError_t e = efx_launch_fundamental(k, d_kps_q + p0, d_kps_t + p0, d_matches + p0, d_nmatches ? d_nmatches + p0 : nullptr,
+                                             q_kps_capacity, t_kps_capacity, capacity, p->hypotheses, p->threshold, p->seed,
+                                             p->refine ? 1 : 0, d_result + p0, d_mask + p0, m->hom.p, st);
+        if (e != hipSuccess) return set_err(m->err, EFX_ERR_HIP, "fundamental launch failed: %s", hipGetErrorString(e));
+    }
+    return EFX_OK;
+}
+
+int efx_match_fundamental_async(efx_matcher* m,
+                               const void* d_kps_q, size_t q_kps_pitch, int q_kps_capacity,
+                               const void* d_kps_t, size_t t_kps_pitch, int t_kps_capacity,
+                               const int* d_matches, const int* d_nmatches, int capacity,
+                               const efx_ransac_params* p, efx_fundamental* d_result, uint8_t* d_mask, void* stream)
+{
+    return efx_match_fundamental_batch_async(m, 1, &d_kps_q, q_kps_pitch, q_kps_capacity, &d_kps_t, t_kps_pitch, t_kps_capacity,
                                             &d_matches, &d_nmatches, capacity, p, &d_result, &d_mask, stream);
 }
 

@@ -498,6 +498,60 @@ public:
             throw Exception(EFX_ERR_HIP, "download failed");
         return r;
     }
+    // cv::findFundamentalMat(src, dst, FM_RANSAC) on matched keypoints, on the device: findHomographyAsync's epipolar
+    // counterpart for scenes with parallax, with the same arguments; x'^T F x ~ 0 (x query, x' train), the threshold is the Sampson
+    // distance in pixels.  The record is NOT a prior for matchGuidedAsync (which predicts a point, not a line).  A planar scene or a
+    // purely rotating camera leaves F undetermined: use findHomographyAsync for those.  No host synchronisation.
+    void findFundamentalAsync(const DeviceMatrix& kpsQ, const DeviceMatrix& kpsT, const DeviceMatrix& matches, const int* d_nmatches,
+                              efx_fundamental* d_result, DeviceMatrix& mask, const efx_ransac_params* params = nullptr,
+                              hipStream_t stream = nullptr)
+    {
+        const efx_ransac_params p = params_or_default(params);
+        mask.create(1, matches.rows > 0 ? matches.rows : 1, 1);
+        check(efx_match_fundamental_async(m_, kpsQ.data(), kpsQ.step, kpsQ.cols, kpsT.data(), kpsT.step, kpsT.cols,
+                                          static_cast<const int*>(matches.data()), d_nmatches, matches.rows, &p, d_result,
+                                          static_cast<uint8_t*>(mask.data()), stream));
+    }
+    // pairs i in one call (seven launches per 16 pairs): every keypoint matrix of one side has one shape, every match list one capacity
+    void findFundamentalBatchAsync(const std::vector<const DeviceMatrix*>& kpsQ, const std::vector<const DeviceMatrix*>& kpsT,
+                                   const std::vector<const DeviceMatrix*>& matches, const std::vector<const int*>& d_nmatches,
+                                   const std::vector<efx_fundamental*>& d_result, std::vector<DeviceMatrix>& masks,
+                                   const efx_ransac_params* params = nullptr, hipStream_t stream = nullptr)
+    {
+        const size_t n = kpsQ.size();
+        if (kpsT.size() != n || matches.size() != n || d_nmatches.size() != n || d_result.size() != n)
+            throw Exception(EFX_ERR_BAD_ARG, "one train matrix, match list, count and result per query matrix");
+        if (n == 0) return;
+        const efx_ransac_params p = params_or_default(params);
+        masks.resize(n);
+        std::vector<const void*> q(n), t(n);
+        std::vector<const int*> mt(n);
+        std::vector<uint8_t*> mk(n);
+        for (size_t i = 0; i < n; i++) {
+            if (kpsQ[i]->cols != kpsQ[0]->cols || kpsQ[i]->step != kpsQ[0]->step || kpsT[i]->cols != kpsT[0]->cols ||
+                kpsT[i]->step != kpsT[0]->step || matches[i]->rows != matches[0]->rows)
+                throw Exception(EFX_ERR_BAD_ARG, "the keypoint matrices of a side and the match lists of a batch have one shape");
+            masks[i].create(1, matches[0]->rows > 0 ? matches[0]->rows : 1, 1);
+            q[i] = kpsQ[i]->data(); t[i] = kpsT[i]->data(); mt[i] = static_cast<const int*>(matches[i]->data());
+            mk[i] = static_cast<uint8_t*>(masks[i].data());
+        }
+        check(efx_match_fundamental_batch_async(m_, (int)n, q.data(), kpsQ[0]->step, kpsQ[0]->cols, t.data(), kpsT[0]->step, kpsT[0]->cols,
+                                                mt.data(), d_nmatches.data(), matches[0]->rows, &p, d_result.data(), mk.data(), stream));
+    }
+    // host convenience: the model and the inlier mask downloaded (one stream synchronisation)
+    efx_fundamental findFundamental(const DeviceMatrix& kpsQ, const DeviceMatrix& kpsT, const DeviceMatrix& matches, const int* d_nmatches,
+                                    std::vector<uint8_t>& mask, const efx_ransac_params* params = nullptr, hipStream_t stream = nullptr)
+    {
+        fres_.create(1, (int)sizeof(efx_fundamental), 1);
+        efx_fundamental* d = static_cast<efx_fundamental*>(fres_.data());
+        findFundamentalAsync(kpsQ, kpsT, matches, d_nmatches, d, hmask_, params, stream);
+        efx_fundamental r;
+        mask.resize((size_t)matches.rows);
+        if (hipStreamSynchronize(stream) != hipSuccess || hipMemcpy(&r, d, sizeof(r), hipMemcpyDeviceToHost) != hipSuccess ||
+            (!mask.empty() && hipMemcpy(mask.data(), hmask_.data(), mask.size(), hipMemcpyDeviceToHost) != hipSuccess))
+            throw Exception(EFX_ERR_HIP, "download failed");
+        return r;
+    }
 private:
     static efx_ransac_params params_or_default(const efx_ransac_params* params)
     {
@@ -511,7 +565,7 @@ private:
         efx_default_guided_params(&p);
         return params ? *params : p;
     }
-    DeviceMatrix hres_, hmask_, gmatches_, ncount_;
+    DeviceMatrix hres_, fres_, hmask_, gmatches_, ncount_;
     void check(int rc) const { if (rc != EFX_OK) throw Exception(rc, efx_matcher_last_error(m_)); }
     efx_matcher* m_ = nullptr;
     bool cross_;

@@ -310,6 +310,37 @@ int efx_match_homography_batch_async(efx_matcher* m, int npairs,
                                      const efx_ransac_params* p, efx_homography* const* d_result, uint8_t* const* d_mask,
                                      void* stream);
 
+/* RANSAC fundamental-matrix verification of matches (cv::findFundamentalMat(src, dst, FM_RANSAC) on the pairs a mutual match keeps),
+ * on the device, one model per pair, DESIGN.md spec S18: the epipolar counterpart of efx_match_homography_async for scenes with
+ * parallax (a camera that moves through a 3-D scene), with the same inputs, count handling, determinism contract and output
+ * shape, so that one call can be swapped for the other.  x'^T F x ~ 0 with x = LOCATION[queryIdx] of the query keypoint matrix and
+ * x' = LOCATION[trainIdx] of the train matrix.  efx_ransac_params is reused: `threshold` is the Sampson distance in pixels; each of
+ * the `hypotheses` samples draws eight rows (splitmix64 of seed + 8 h + j), so an all-inlier sample has probability w^8 (w = the
+ * inlier share) against w^4 for the homography: budget accordingly.  refine = 1: a normalised eight-point refit of rank 2 on the
+ * winner's inliers (at least 8).  A planar scene or a purely rotating camera leaves F undetermined; the call still returns a model
+ * consistent with the points, but efx_match_homography_async is the model for those.  An efx_fundamental record has the size and
+ * alignment of an efx_homography record but is NOT a prior for efx_match_guided_async, which predicts a point, not a line.
+ * Argument checks, error codes, NULL rules and synchronisation are those of the homography calls. */
+typedef struct efx_fundamental {    /* written on the device, one per pair; same layout as efx_homography (88 bytes) */
+    double F[9];                    /* row-major, x'^T F x = 0, the entry of largest magnitude == 1; all 0 without a model */
+    int ninliers, hypothesis;       /* the winner's inlier count and index (-1: no model) */
+    int valid_hypotheses, refined;  /* hypotheses that passed the sample checks; 1 if F is the rank-2 refit */
+} efx_fundamental;
+int efx_match_fundamental_async(efx_matcher* m,
+                                const void* d_kps_q, size_t q_kps_pitch, int q_kps_capacity,
+                                const void* d_kps_t, size_t t_kps_pitch, int t_kps_capacity,
+                                const int* d_matches, const int* d_nmatches, int capacity,
+                                const efx_ransac_params* p, efx_fundamental* d_result, uint8_t* d_mask, void* stream);
+/* npairs pairs in one call: the arguments above as tables of npairs pointers (d_nmatches may be NULL: every count = capacity).
+ * Seven launches (five without the refit) per chain of up to EFX_MAX_BATCH = 16 pairs (pair = blockIdx.z); every pair's output
+ * equals efx_match_fundamental_async's on it, bit for bit. */
+int efx_match_fundamental_batch_async(efx_matcher* m, int npairs,
+                                      const void* const* d_kps_q, size_t q_kps_pitch, int q_kps_capacity,
+                                      const void* const* d_kps_t, size_t t_kps_pitch, int t_kps_capacity,
+                                      const int* const* d_matches, const int* const* d_nmatches, int capacity,
+                                      const efx_ransac_params* p, efx_fundamental* const* d_result, uint8_t* const* d_mask,
+                                      void* stream);
+
 /* Guided (spatially gated) mutual matching on the device, DESIGN.md spec S17: the filter of efx_match_mutual_async with both knnMatch
  * directions restricted to the candidate pairs C.  Pair (i, j) is in C iff train j lies in the square window of `radius` pixels
  * (inclusive) around the position predicted for query i, and -- with max_octave_diff >= 0 -- |octave_i - octave_j| <=
